@@ -18,6 +18,11 @@ steps of its own queries; --scaling strong: the SAME steps x group queries are s
 One JSON line on rank 0; see the prompt contract.  `roofline` is for the dominant kernel (gapless scan) from HIP
 events around that kernel on the library's stream; `cpu_baseline` times the reference's own AVX2 code (oracle/_ref,
 kind "reference") or, if that was not built, the C port (oracle/libfso.so) on a bounded sample of the same workload.
+
+A plain run does only what the headline figure needs: set-up, warm-up, the --steps timed steps, the line.  --full adds
+the rest (solo probes, CPU baselines, the other configurations' legs, the one-rank RCCL check).  --dump-outputs DIR
+writes the hit lists and alignment results of the last timed step as float64 .npy files, so that two builds can be
+compared output for output (the inputs are seeded: the same arguments give the same queries and DB).
 """
 import argparse
 import json
@@ -94,7 +99,36 @@ def parse(argv=None):
     ap.add_argument("--allvsall-batch", type=int, default=1024, help="queries per device batch of the all-vs-all leg (1024 = the limit of a device batch)")
     ap.add_argument("--emulate-rank-share", type=int, default=0, help="N: on ONE GPU, run what ONE rank of an N-rank node runs: CPU affinity cut to usable_cores / N, "
                     "backtrace pool sized for that, and with --scaling strong only 1/N of the queries (step size adapted like a real rank's)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline figure: the one-rank RCCL check at N = 1, solo probes, CPU baselines and the "
+                    "type-2, full-length-range, k-mer, single-query and all-vs-all legs (without it a run sets up, warms up, times --steps steps and prints its line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step returned (hit lists and alignment "
+                    "results, one field per file) as DIR/<name>.npy in float64")
     return ap.parse_args(argv)
+
+
+DUMP_LIMIT = 64 << 20
+
+
+def result_arrays(prefix, lists):
+    """one query's arrays after the other: `<prefix>_per_query` (their lengths) + one flat array per field of the records
+    (padding and backtraceOff, an offset into the search handle's CIGAR buffer, are not results)"""
+    out = {f"{prefix}_per_query": np.array([len(x) for x in lists], np.float64)}
+    cat = np.concatenate(lists)
+    for f in cat.dtype.names:
+        if not f.startswith("_") and f != "backtraceOff":
+            out[f"{prefix}_{f}"] = cat[f]
+    return out
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy in float64 (exact for the int32 / uint32 / float32 fields of the records)"""
+    arrays = {k: np.ascontiguousarray(v, np.float64) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (limit {DUMP_LIMIT})")
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
 
 
 def relaunch_as_ranks(args):
@@ -445,12 +479,12 @@ def allvsall_db(synth, targets, families):
     return synth.make_db_fast(targets, seeds, seed=20260923, homologs_per_query=max(targets // families - 1, 1))
 
 
-def allvsall_run(args, api, synth, fdist, dev, rank, world, local_rank, targets, steps, warmup, with_cpu=False):
+def allvsall_run(args, api, synth, fdist, dev, rank, world, local_rank, targets, steps, warmup, with_cpu=False, probes=True, dump=None):
     """configs[4]: all-vs-all of a `targets`-structure DB, the shape of easy-cluster's cascaded steps (F/data/structurecluster.sh via
     `easy-cluster -v 3`): prefilter -s 4.5 --max-seqs 200 --min-ungapped-score 30 -c 0.8 --add-self-matches 1, then structurealign
     -e 0.01 -c 0.8 --comp-bias-corr 0.  Prefilter dominated: one pass of the k-mer index per batch of 32 queries.  Every DB entry is a
     query; the ids shard over the ranks (`steps` batches each, 0 = all of them), the DB is replicated by one broadcast.  Returns the
-    result object on rank 0 (None elsewhere)."""
+    result object on rank 0 (None elsewhere).  probes: the solo runs of one batch for the rooflines; dump: --dump-outputs DIR (rank 0)."""
     import threading
     import torch
     import torch.distributed as dist
@@ -500,6 +534,7 @@ def allvsall_run(args, api, synth, fdist, dev, rank, world, local_rank, targets,
         warm, timed = batches[:1], batches
     stat = {"hits": 0, "aln": 0, "q": 0, "res": 0, "dev": 0.0, "bad": 0, "stage": np.zeros(11), "cnt": np.zeros(4), "nb": 0, "swp": [], "diag_bytes": 0.0}
     lock = threading.Lock()
+    last = {}               # what the last timed batch returned (--dump-outputs)
 
     # the queries are DB entries: unmasked code strings once, then a batch is two arrays of host addresses -- no per-query work in the interpreter;
     # profiles, device prefilter, coverage pre-filter and alignment of a batch are ONE library call (fshost_search_kmer_batch, the per-batch body
@@ -521,6 +556,8 @@ def allvsall_run(args, api, synth, fdist, dev, rank, world, local_rank, targets,
         swp = ctxs[t].sw_last_passes()
         btc = searches[t].backtrace_counts()
         if count:
+            if timed and b is timed[-1]:
+                last["r"] = r
             sec = r["seconds"]
             with lock:
                 stat["bt_device"] = stat.get("bt_device", 0) + btc[0]; stat["bt_all"] = stat.get("bt_all", 0) + btc[1]
@@ -568,7 +605,7 @@ def allvsall_run(args, api, synth, fdist, dev, rank, world, local_rank, targets,
         raise RuntimeError(f"all-vs-all leg: a feeder thread failed: {failed[0]!r}") from failed[0]
     # one batch alone on the device (the middle one of this rank's timed batches): the solo figures of both rooflines
     solo = None
-    if timed:
+    if timed and probes:
         keep_stat = {k: (v.copy() if hasattr(v, "copy") else v) for k, v in stat.items()}
         best, best_sw = None, None
         sw_ms = lambda p: sum(float(p[d][0]) for d in (0, 1) if p[d][0] >= 0)
@@ -586,6 +623,11 @@ def allvsall_run(args, api, synth, fdist, dev, rank, world, local_rank, targets,
     mine_swp = stat.pop("swp")
     tot = fdist.gather_objects(stat)
     out = None
+    if rank == 0 and dump and "r" in last:
+        r, n = last["r"], len(timed[-1])
+        dump_outputs(dump, {"status": r["status"][:n], "prefilter_kept_per_query": r["nkept"][:n],
+                            "prefilter_kept_id": np.concatenate([r["kept"][i, :r["nkept"][i]] for i in range(n)]),
+                            **result_arrays("align", [r["results"][i, :r["nres"][i]] for i in range(n)])})
     if rank == 0:
         nq = sum(x["q"] for x in tot)
         s0 = tot[0]
@@ -710,7 +752,8 @@ def single_query_leg(args, api, synth, local_rank, with_cpu):
 def search_region(api, ctxs, searches, q3, qa, warm_batches, batches, world, dev, fdist, class_warm, nq_all):
     """The timed region of one search leg: every feeder thread (own context clone = own HIP stream, shared resident DB) runs its share of
     `batches`; a step = ONE multi-query scan call for the batch (queries of equal ceil(L / 16) share a launch), then ONE multi-query SW
-    launch per pass over all their hit lists.  Bracketed by barrier + device synchronisation on both sides, max over ranks."""
+    launch per pass over all their hit lists.  Bracketed by barrier + device synchronisation on both sides, max over ranks.
+    rec["last"] = (hit lists, alignment results) of the last batch of `batches` (--dump-outputs)."""
     import gc
     import threading
     import torch
@@ -762,6 +805,8 @@ def search_region(api, ctxs, searches, q3, qa, warm_batches, batches, world, dev
             swp = ctxs[t].sw_last_passes()
             btc = searches[t].backtrace_counts()
             with lock:
+                if b is batches[-1]:
+                    rec["last"] = (hl, rs)
                 if os.environ.get("FS_BENCH_TRACE"):
                     rec["trace"].append((t, tg - t_go[0], time.perf_counter() - tg))
                 rec["kms"].append(km); rec["sms"].append(ctxs[t].kernel_ms(1) / len(b)); rec["swp"].append(swp)
@@ -865,12 +910,12 @@ def main():
             dist.init_process_group("nccl", device_id=torch.device("cuda", dev_index))
         else:
             dist.init_process_group(backend)
-    # One GPU: the DB "broadcast" still goes through a (one-rank) RCCL communicator, so that the transport the N-GPU run depends on has run and the
-    # line says so (`broadcast_backend: nccl, rccl_ranks: 1`).  Default since round 5; FSGPU_REQUIRE_RCCL=1 makes a failure fatal, =0 skips it.
+    # One GPU: with --full the DB "broadcast" still goes through a (one-rank) RCCL communicator, so that the transport the N-GPU run depends on has run
+    # and the line says so (`broadcast_backend: nccl, rccl_ranks: 1`).  FSGPU_REQUIRE_RCCL=1 asks for it in any run and makes a failure fatal, =0 skips it.
     rq = os.environ.get("FSGPU_REQUIRE_RCCL", "")
     require_rccl = rq not in ("", "0")
     rccl_note = None
-    if world == 1 and rq != "0" and have_gpu and not dist.is_initialized() and not args.dry_run:
+    if world == 1 and rq != "0" and (args.full or require_rccl) and have_gpu and not dist.is_initialized() and not args.dry_run:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         os.environ.setdefault("MASTER_PORT", str(29500 + os.getpid() % 2000))
         try:
@@ -886,7 +931,8 @@ def main():
 
     if args.workload == "allvsall" and not args.dry_run:
         from foldseek_amd import api
-        out = allvsall_run(args, api, synth, fdist, dev, rank, world, local_rank, args.targets, args.steps, args.warmup, with_cpu=(world == 1 and not args.no_cpu_baseline))
+        out = allvsall_run(args, api, synth, fdist, dev, rank, world, local_rank, args.targets, args.steps, args.warmup,
+                           with_cpu=(args.full and world == 1 and not args.no_cpu_baseline), probes=args.full, dump=args.dump_outputs)
         if rank == 0:
             emit_line(out)
         if world > 1:
@@ -901,7 +947,8 @@ def main():
     n_warm = args.warmup * G
     q_lo, q_hi = (int(x) for x in args.query_len.split(","))
     all_q3, all_qa = synth.make_queries(n_timed_total + world * n_warm, seed=1000, lo=q_lo, hi=q_hi)   # default 250..450: around the mean length 350; same on every rank
-    # querylen_full_range leg: queries over the DB's own length range (30..2000), their homologs planted like everybody's
+    # querylen_full_range leg (--full): queries over the DB's own length range (30..2000), their homologs planted like everybody's; they are
+    # generated and planted in every run, so that the DB of a plain run is the DB of a --full one
     n_full = max(0, args.fullrange_steps) * G if (q_lo, q_hi) != (30, 2000) and not args.dry_run else 0
     fr_q3, fr_qa = synth.make_queries(n_full * world, seed=3000, lo=30, hi=2000) if n_full else ([], [])
     phase = {}
@@ -1012,17 +1059,20 @@ def main():
     mark("device_open")
     dt, rec, step = search_region(api, ctxs, searches, q3, qa, warm, batches, world, dev, fdist, True, nq)
     mark("main_region_with_warmup")
+    if args.dump_outputs and rank == 0:
+        hl, rs = rec["last"]
+        dump_outputs(args.dump_outputs, {**result_arrays("prefilter", hl), **result_arrays("align", rs)})
     kms, sms, counts, host = rec["kms"], rec["sms"], rec["counts"], rec["host"]
-    # dominant-kernel duration on an otherwise idle GPU (in the timed region the feeder threads' launches overlap, which
+    # --full: dominant-kernel duration on an otherwise idle GPU (in the timed region the feeder threads' launches overlap, which
     # stretches each kernel's wall time)
     solo_g, solo_s = [], []
-    for i in range(n_warm, min(nq, n_warm + 8)):
+    for i in range(n_warm, min(nq, n_warm + 8) if args.full else n_warm):
         step1(0, i)
         solo_g.append(ctxs[0].kernel_ms(0)); solo_s.append(ctxs[0].kernel_ms(1))
     # one whole batch alone on the device, three times: the SW passes' solo figure is their fastest repetition (a single one moved by +-10 % from run to run)
     solo_swp = None
     _sw_ms = lambda p: sum(float(p[d][0]) for d in (0, 1) if p[d][0] >= 0)
-    for _ in range(3):
+    for _ in range(3 if args.full else 0):
         step(0, batches[len(batches) // 2])
         p_ = ctxs[0].sw_last_passes()
         if solo_swp is None or _sw_ms(p_) < _sw_ms(solo_swp):
@@ -1063,20 +1113,21 @@ def main():
         nh, nr = sum(x[0] for x in tot), sum(x[1] for x in tot)
         value = nq_total * residues / dt
         VALU_PEAK = 1024 * 64 * (4.0 / 3.0) / 4.3 * 2.4
-        kavg = float(np.mean(solo_g)) * 1e-3
+        kavg = float(np.mean(solo_g)) * 1e-3 if solo_g else None
         lq_timed = [len(q3[i]) for i in timed]
-        solo_lq = float(np.mean([len(q3[i]) for i in range(n_warm, min(nq, n_warm + 8))]))
+        solo_lq = float(np.mean([len(q3[i]) for i in range(n_warm, min(nq, n_warm + 8))])) if solo_g else None
         alg_q = residues + db.n
         mean_lq = float(np.mean(lq_timed))
-        cells = solo_lq * residues
+        cells = solo_lq * residues if solo_g else None
         mine = tot[0][3]
         rf = gapless_roofline(kms, lq_timed)
         rf["valu"].update({"device_level_gcups": nq_total / world * mean_lq * residues / dt / 1e9,
                            "device_level_frac": nq_total / world * mean_lq * residues / dt / 1e9 / VALU_PEAK,
                            "device_level_frac_ideal_4cyc": nq_total / world * mean_lq * residues / dt / 1e9 / (VALU_PEAK * 4.3 / 4.0),
                            "note": "per launch = one multi-query k_gapless launch (scan batches of the feeder threads run one at a time, SW / selection kernels of the other threads co-run); device_level = cells of all timed queries of one rank / wall time"})
-        rf["solo"] = {"note": "one single-query launch on an idle device", "kernel_ms": kavg * 1e3, "achieved": alg_q / kavg / 1e9, "frac": alg_q / kavg / 1e9 / 8000.0,
-                      "valu_achieved_gcups": cells / kavg / 1e9, "valu_frac": cells / kavg / 1e9 / VALU_PEAK}
+        if solo_g:
+            rf["solo"] = {"note": "one single-query launch on an idle device", "kernel_ms": kavg * 1e3, "achieved": alg_q / kavg / 1e9, "frac": alg_q / kavg / 1e9 / 8000.0,
+                          "valu_achieved_gcups": cells / kavg / 1e9, "valu_frac": cells / kavg / 1e9 / VALU_PEAK}
         out = {
             "metric": "residues aligned/sec (prefilter+align)",
             "value": value, "unit": "residues/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -1102,7 +1153,7 @@ def main():
                           "host_gates_ms_per_query": 1e3 * mine["gates_s"] / max(1, n_mine),
                           "host_profiles_ms_per_query": 1e3 * mine["profiles_s"] / max(1, n_mine),
                           "sw_call_wall_ms_per_query": 1e3 * mine["sw_wait_s"] / max(1, n_mine),
-                          "sw_kernels_ms_per_query": float(np.mean(sms)), "sw_kernel_ms_single_query_solo": float(np.mean(solo_s)),
+                          "sw_kernels_ms_per_query": float(np.mean(sms)), "sw_kernel_ms_single_query_solo": float(np.mean(solo_s)) if solo_s else None,
                           "roofline": sw_roofline(rec["swp"], args.alignment_type == 2, solo_swp, args.targets)},
             # per-launch duration of the dominant kernel from HIP events on the library's stream, averaged over the launches
             # of the TIMED region (the host threads overlap their launches there, which stretches each one); the same
@@ -1116,15 +1167,16 @@ def main():
             out["emulated_rank_share"] = {"ranks": emu, "cores_of_this_rank": usable_cores(), "cores_of_the_job": cores_before,
                                           "timed_queries_of_this_rank": n_mine, "projected_value_all_ranks": emu * value,
                                           "note": "ONE rank's share of an N-rank node run on one GPU: value is this rank's rate; with a replicated DB and no per-step collective the ranks do not interact"}
-        if not args.no_cpu_baseline and world == 1:          # the CPU baselines are an N = 1 item (rank 0 has the host to itself)
+        if args.full and not args.no_cpu_baseline and world == 1:          # the CPU baselines are an N = 1 item (rank 0 has the host to itself)
             hits, _ = step1(0, n_warm)
             out["cpu_baseline"] = cpu_baseline(db, q3[n_warm], qa[n_warm], hits["id"], args.alignment_type, args.cpu_sample_targets,
                                                [q3[i] for i in range(n_warm + 1, min(nq, n_warm + max(1, args.cpu_sample_queries)))])
             t_pref_cpu = out["cpu_baseline"].get("prefilter_s_sample")
     mark("solo_probes_and_cpu_baseline")
 
+    # ---- the legs below and the CPU baselines are --full only ----
     # ---- configs[3]: the same search with --alignment-type 2 (3Di + AA substitution scores, Gotoh affine gaps) on the resident DB ----
-    if args.type2_steps > 0 and args.alignment_type != 2:
+    if args.full and args.type2_steps > 0 and args.alignment_type != 2:
         try:
             par2 = api.default_params()
             par2.alignmentType = 2
@@ -1166,7 +1218,7 @@ def main():
 
     mark("align_type2_leg")
     # ---- the DB's own query length range (30..2000): short queries pair up in a scan kernel, queries beyond 896 residues run row-tiled ----
-    if n_full > 0:
+    if args.full and n_full > 0:
         try:
             f3, fa = fr_q3[rank * n_full:(rank + 1) * n_full], fr_qa[rank * n_full:(rank + 1) * n_full]
             order = sorted(range(n_full), key=lambda i: len(f3[i]))
@@ -1198,7 +1250,7 @@ def main():
         c.close()
     searches, ctxs = searches[:1], ctxs[:1]
     kout = None
-    if not args.no_kmer:
+    if args.full and not args.no_kmer:
         # the legs after the main line are additional evidence: on one GPU a failure in one of them is recorded in its place instead of
         # costing the whole line (with several ranks the others would wait in a collective: there the error propagates)
         try:
@@ -1218,14 +1270,14 @@ def main():
         c.close()
     del db
     # ---- configs[1]: one query at a time against a 100k-structure DB (latency), rank 0's GPU only ----
-    if args.single_targets > 0 and rank == 0:
+    if args.full and args.single_targets > 0 and rank == 0:
         try:
             out["single_query_100k"] = single_query_leg(args, api, synth, local_rank, with_cpu=(world == 1 and not args.no_cpu_baseline))
         except Exception as e:                                             # noqa: BLE001
             out["single_query_100k"] = {"error": repr(e)[:500]}
     mark("single_query_leg")
     # ---- configs[4]: all-vs-all of a 200k-structure DB (easy-cluster's prefilter + align step), own DB, same process ----
-    if args.allvsall_steps > 0:
+    if args.full and args.allvsall_steps > 0:
         try:
             av = allvsall_run(args, api, synth, fdist, dev, rank, world, local_rank, args.allvsall_targets, args.allvsall_steps, 8,
                               with_cpu=(world == 1 and not args.no_cpu_baseline))

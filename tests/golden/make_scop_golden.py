@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """tests/golden/make_scop_golden.py -- generator of tests/golden/scop_v1 (TEST INFRASTRUCTURE).
 
-Runs the WHOLE reference binary (oracle/_ref_full/bin/foldseek, built from a patched out-of-tree copy of
-/root/reference by oracle/build_ref_full.sh) on the reference's own example structures (F/example: 25 SCOP domains +
+Runs the WHOLE reference binary (oracle/_ref/bin/foldseek, built from a patched out-of-tree copy of
+the reference tree by oracle/build_ref_full.sh) on the reference's own example structures (F/example: 25 SCOP domains +
 1tim/8tim) and freezes
 
   * the databases the reference's `createdb` and `makepaddedseqdb` WRITE (db, db_ss, db_h, db_pad*, with .index /
@@ -22,7 +22,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-FS = os.path.join(ROOT, "oracle", "_ref_full", "bin", "foldseek")
+FS = os.path.join(ROOT, "oracle", "_ref", "bin", "foldseek")
 EXAMPLE = "/root/reference/example"
 OUT = os.path.join(HERE, "scop_v1")
 

@@ -20,7 +20,7 @@ from foldseek_amd import dbio
 from test_modules_vs_reference_binary import BIN, FS, MANIFEST, _run, _same
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not os.path.exists(FS), reason="oracle/_ref_full/bin/foldseek not built")]
+pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not os.path.exists(FS), reason="oracle/_ref/bin/foldseek not built")]
 
 N, FAMILIES, NQ = 200000, 20000, 1024
 CASCADE = [("-s", "1", "--max-seqs", "100", "--diag-score", "0", "--min-ungapped-score", "0"),

@@ -63,6 +63,11 @@ def test_broadcast_and_query_sharding_world2():
         assert keys == sel["key"].tolist() and scores == sel["score"].tolist()
 
 
+# the bench runs below are the CPU plumbing (gloo) wherever the suite runs: on a one-GPU machine `--gpus N` over RCCL would (rightly)
+# refuse to put N ranks on one device, so the device is hidden from them, and the backend is named in case it is not
+_NO_GPU = {"HIP_VISIBLE_DEVICES": "-1", "FSGPU_BENCH_BACKEND": "gloo"}
+
+
 @pytest.mark.parametrize("scaling", ["weak", "strong"])
 def test_bench_gpus2_dry_run_starts_two_ranks(scaling):
     """`python bench.py --gpus 2` (no torchrun around it) must come up with two ranks through the BENCH code path: the
@@ -73,6 +78,7 @@ def test_bench_gpus2_dry_run_starts_two_ranks(scaling):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env.update(_NO_GPU)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--dry-run", "--targets", "2500", "--steps", "3",
                         "--warmup", "1", "--group", "4", "--scaling", scaling], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
                        env=env, timeout=600)
@@ -94,6 +100,7 @@ def test_bench_gpus8_dry_run_strong_scaling_shares():
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env.update(_NO_GPU)
     env["OMP_NUM_THREADS"] = "1"
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--dry-run", "--targets", "2000", "--steps", "16",
                         "--warmup", "1", "--group", "64", "--scaling", "strong"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,

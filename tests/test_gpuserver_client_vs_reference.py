@@ -1,6 +1,6 @@
 """The gpuserver protocol's CLIENT half against the reference's own client, no GPU needed: a scripted server (this test) owns the
 shared-memory block under the name both binaries derive from (database path, visible devices, version string) and answers every READY with a
-result list that depends on the query.  The reference binary (oracle/_ref_full/bin/foldseek-fsgpu: its unmodified ungappedprefilter.cpp /
+result list that depends on the query.  The reference binary (oracle/_ref/bin/foldseek-fsgpu: its unmodified ungappedprefilter.cpp /
 GpuUtil.cpp) and `fsgpu-modules ungappedprefilter --gpu-server 1` must
   * hand over the same bytes for every query -- residue codes and the 21 x L int8 profile incl. the composition bias -- and
   * write byte-identical prefilter DBs from the same answers (threshold, order, --max-seqs cut, text format)."""
@@ -20,10 +20,10 @@ import pytest
 from foldseek_amd import api
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FS_GPU = os.path.join(ROOT, "oracle", "_ref_full", "bin", "foldseek-fsgpu")
+FS_GPU = os.path.join(ROOT, "oracle", "_ref", "bin", "foldseek-fsgpu")
 BIN = os.path.join(ROOT, "foldseek_amd", "bin", "fsgpu-modules")
 GOLD = os.path.join(ROOT, "tests", "golden", "scop_v1")
-pytestmark = pytest.mark.skipif(not os.path.exists(FS_GPU), reason="oracle/_ref_full/bin/foldseek-fsgpu not built (oracle/build_ref_full.sh gpu)")
+pytestmark = pytest.mark.skipif(not os.path.exists(FS_GPU), reason="oracle/_ref/bin/foldseek-fsgpu not built (oracle/build_ref_full.sh gpu)")
 
 
 class ScriptedServer:

@@ -1,5 +1,5 @@
-"""Host-only modules against the reference BINARY, no GPU needed (runs wherever oracle/_ref_full/bin/foldseek exists: this container and the
-GPU box): makepaddedseqdb on a database full of edge cases -- empty entries, one-residue entries, X, soft-masked residues, lengths around the
+"""Host-only modules against the reference BINARY, no GPU needed (runs wherever oracle/_ref/bin/foldseek was built, with or without a
+GPU): makepaddedseqdb on a database full of edge cases -- empty entries, one-residue entries, X, soft-masked residues, lengths around the
 4-byte padding, headers with database prefixes -- must write the same seven files byte for byte."""
 import os
 import subprocess
@@ -10,9 +10,9 @@ import pytest
 from foldseek_amd import dbio
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FS = os.path.join(ROOT, "oracle", "_ref_full", "bin", "foldseek")
+FS = os.path.join(ROOT, "oracle", "_ref", "bin", "foldseek")
 BIN = os.path.join(ROOT, "foldseek_amd", "bin", "fsgpu-modules")
-pytestmark = pytest.mark.skipif(not os.path.exists(FS), reason="oracle/_ref_full/bin/foldseek not built")
+pytestmark = pytest.mark.skipif(not os.path.exists(FS), reason="oracle/_ref/bin/foldseek not built")
 
 
 def _sorted_index(path):

@@ -1,6 +1,6 @@
 """`indexdb` / `createindex`: the precomputed index this repository writes -- sequence / header DBs, masked sequence
 lookup, the k-mer table built on the device and renumbered to the reference's k-mer order, the extended 2- and 3-mer matrices -- against the
-one the reference BINARY (oracle/_ref_full/bin/foldseek, built by oracle/build_ref_full.sh, travels to the GPU box) writes for the same DB
+one the reference BINARY (oracle/_ref/bin/foldseek, built by oracle/build_ref_full.sh next to the other built checkers) writes for the same DB
 with the same parameter string, entry by entry (tests/idx_compare.py), and FUNCTIONALLY: the reference's CPU prefilter run on OUR index
 returns what it returns on its own."""
 import json
@@ -16,9 +16,9 @@ from idx_compare import compare
 from test_scop_golden import BIN, GOLD, read_db
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FS = os.path.join(ROOT, "oracle", "_ref_full", "bin", "foldseek")
+FS = os.path.join(ROOT, "oracle", "_ref", "bin", "foldseek")
 MANIFEST = json.load(open(os.path.join(GOLD, "MANIFEST.json")))
-pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not os.path.exists(FS), reason="oracle/_ref_full/bin/foldseek not built")]
+pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not os.path.exists(FS), reason="oracle/_ref/bin/foldseek not built")]
 
 
 def _run(cmd, cwd):

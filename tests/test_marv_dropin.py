@@ -1,6 +1,6 @@
 """The boundary that LINKS: the reference's own binary, built from its unmodified sources with -DHAVE_CUDA=1 and this
 repository's `class Marv` (include/marv.h + foldseek_amd/csrc/host/marv_shim.cpp over libfsgpu.so) in place of libmarv
-(oracle/build_ref_full.sh gpu -> oracle/_ref_full/bin/foldseek-fsgpu, a built file that travels to the GPU box).
+(oracle/build_ref_full.sh gpu -> oracle/_ref/bin/foldseek-fsgpu, a built file next to the other built checkers).
 
 Here the REFERENCE's runFilterOnGpu (M/src/prefiltering/ungappedprefilter.cpp:41-326), its gpuserver
 (M/src/util/gpuserver.cpp:24-101) and its shared-memory client run on the MI355X through Marv::scan, on the
@@ -17,8 +17,8 @@ import pytest
 from test_scop_golden import GOLD, MANIFEST, read_db, scop  # noqa: F401  (scop is a fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FS_GPU = os.path.join(ROOT, "oracle", "_ref_full", "bin", "foldseek-fsgpu")
-pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not os.path.exists(FS_GPU), reason="oracle/_ref_full/bin/foldseek-fsgpu not built (oracle/build_ref_full.sh gpu)")]
+FS_GPU = os.path.join(ROOT, "oracle", "_ref", "bin", "foldseek-fsgpu")
+pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not os.path.exists(FS_GPU), reason="oracle/_ref/bin/foldseek-fsgpu not built (oracle/build_ref_full.sh gpu)")]
 
 
 def _env():

@@ -319,7 +319,7 @@ def test_single_gpu_paths_run_through_rccl_when_required(tmp_path):
     if ngpu == 1:
         bad = subprocess.run(cmd, cwd=tmp_path, env=dict(env, FSGPU_NO_RCCL="1"), capture_output=True, text=True)
         assert bad.returncode == 0            # FSGPU_NO_RCCL is the explicit opt-out: no check, no failure
-    b = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--targets", "20000", "--no-kmer", "--type2-steps", "0",
+    b = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--steps", "2", "--warmup", "1", "--targets", "20000", "--no-kmer", "--type2-steps", "0",
                         "--allvsall-steps", "0", "--fullrange-steps", "0", "--no-cpu-baseline"], env=env, capture_output=True, text=True, cwd=ROOT)
     assert b.returncode == 0, b.stderr[-3000:]
     line = json.loads([l for l in b.stdout.splitlines() if l.startswith("{")][-1])

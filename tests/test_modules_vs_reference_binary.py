@@ -1,5 +1,5 @@
-"""Module-level cross-check AT SCALE against the reference BINARY (oracle/_ref_full/bin/foldseek, the whole reference built by
-oracle/build_ref_full.sh; a built file that travels to the GPU box): both read the SAME on-disk databases (3000 synthetic targets
+"""Module-level cross-check AT SCALE against the reference BINARY (oracle/_ref/bin/foldseek, the whole reference built by
+oracle/build_ref_full.sh; a built file next to the other built checkers): both read the SAME on-disk databases (3000 synthetic targets
 up to 1200 residues with soft-masked stretches, 48 queries with planted homologs), the reference runs its CPU modules with the
 workflow's complete parameter strings, `fsgpu-modules` gets the same argument vectors, and every entry of every result DB must be
 byte-identical: k-mer prefilter, ungapped prefilter (plain and reference-padded target), structurealign on both (3Di+AA and 3Di
@@ -27,9 +27,9 @@ from foldseek_amd import dbio, synth
 from test_scop_golden import BIN, GOLD, read_db
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FS = os.path.join(ROOT, "oracle", "_ref_full", "bin", "foldseek")
+FS = os.path.join(ROOT, "oracle", "_ref", "bin", "foldseek")
 MANIFEST = json.load(open(os.path.join(GOLD, "MANIFEST.json")))
-pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not os.path.exists(FS), reason="oracle/_ref_full/bin/foldseek not built")]
+pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not os.path.exists(FS), reason="oracle/_ref/bin/foldseek not built")]
 
 
 def _run(cmd, cwd, env=None):

@@ -15,11 +15,11 @@ import pytest
 from test_scop_golden import MANIFEST, read_db, scop  # noqa: F401  (scop is a fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FS_GPU = os.path.join(ROOT, "oracle", "_ref_full", "bin", "foldseek-fsgpu")
-FS_CPU = os.path.join(ROOT, "oracle", "_ref_full", "bin", "foldseek")
+FS_GPU = os.path.join(ROOT, "oracle", "_ref", "bin", "foldseek-fsgpu")
+FS_CPU = os.path.join(ROOT, "oracle", "_ref", "bin", "foldseek")
 EXAMPLES = os.path.join(ROOT, "tests", "golden", "example_structures")
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not (os.path.exists(FS_GPU) and os.path.exists(FS_CPU)),
-                                                  reason="oracle/_ref_full/bin/foldseek{,-fsgpu} not built (oracle/build_ref_full.sh all)")]
+                                                  reason="oracle/_ref/bin/foldseek{,-fsgpu} not built (oracle/build_ref_full.sh all)")]
 
 
 def _env():

@@ -169,11 +169,11 @@ def test_rescorediagonal_undefined_pairs_are_refused_or_skipped(scop):
     assert read_db(out) == read_db(str(scop / "resc_t2_a"))
 
 
-FS_REF = os.path.join(ROOT, "oracle", "_ref_full", "bin", "foldseek")
+FS_REF = os.path.join(ROOT, "oracle", "_ref", "bin", "foldseek")
 
 
 @pytest.mark.gpu
-@pytest.mark.skipif(not os.path.exists(FS_REF), reason="oracle/_ref_full/bin/foldseek not built (oracle/build_ref_full.sh cpu)")
+@pytest.mark.skipif(not os.path.exists(FS_REF), reason="oracle/_ref/bin/foldseek not built (oracle/build_ref_full.sh cpu)")
 def test_modules_take_precomputed_indexes_as_targets(scop):
     """SURVEY 8f rank 4.  Once `createindex` has run, the search workflow hands the modules the INDEX as target
     (`prefilter db_ss db_ss.idx`, `structurealign db db.idx`, F/data/structuresearch.sh "${TARGET_PREFILTER}${INDEXEXT}").  The indexes

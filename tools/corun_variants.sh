@@ -1,7 +1,7 @@
 #!/bin/bash
 # The batch SW next to the other feeders' scans under different device-sharing schemes: tools/corun_variants.sh "ENV=V ..." ...
 # Each variant: main leg (configs[2], 20 steps of 64 queries) + the --alignment-type 2 leg (12 steps), nothing else.
-for v in "$@"; do echo "== $v"; env $v python bench.py --no-cpu-baseline --no-kmer --allvsall-steps 0 --fullrange-steps 0 --single-targets 0 2>/dev/null | python -c "
+for v in "$@"; do echo "== $v"; env $v python bench.py --full --no-cpu-baseline --no-kmer --allvsall-steps 0 --fullrange-steps 0 --single-targets 0 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 r=d['align_leg']['roofline']; t=d['align_type2']; r2=t['align_roofline']

@@ -1,5 +1,5 @@
 mkdir -p gpurun_out/r06_prof
-for v in ${BT_MODES:-"FSGPU_DEVICE_BACKTRACE=0" "X=auto"}; do echo "== $v"; env $v python bench.py --emulate-rank-share 8 --scaling weak 2>/dev/null > /tmp/emu_out.json; python - <<'PY'
+for v in ${BT_MODES:-"FSGPU_DEVICE_BACKTRACE=0" "X=auto"}; do echo "== $v"; env $v python bench.py --full --emulate-rank-share 8 --scaling weak 2>/dev/null > /tmp/emu_out.json; python - <<'PY'
 import json
 d=json.loads(open('/tmp/emu_out.json').read().strip().splitlines()[-1])
 a=d['allvsall']; k=d['kmer_prefilter']
