@@ -1,8 +1,11 @@
 // fsgpu_ctx.h -- private: the context / database structures shared by the translation units of libfsgpu.so.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <chrono>
 #include <cstdlib>
+#include <cstring>
+#include <initializer_list>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -47,7 +50,7 @@ struct DbStore {
     int32_t *dLengths = nullptr;
     std::vector<int32_t> hLengths;
     // gapless work lists, one per overlap class (index = overlap in 16-column chunks, 0 = whole stripes): built on first
-    // use by gaplessItems() (fsgpu.hip), shared by all contexts of this DB
+    // use by gaplessItems() (fsgpu_gapless.hip), shared by all contexts of this DB
     std::vector<uint32_t> hStripeLen;
     struct ItemList { uint4 *items = nullptr; uint32_t n = 0; bool split = false, built = false; };
     ItemList itemLists[kGaplessMaxRUntiled + 1];
@@ -82,7 +85,7 @@ struct fsgpu_ctx {
     double kmerHitsPerQuery = 0;       // index hits per query of the last batch (sizes the next one)
     double kmerKPerPos = 0;            // similar k-mers per query position of the last batch (picks the wave / workgroup form of the next count pass)
     int kmerBatchCap = 0;              // > 0: a batch overflowed 2^32 hits, stay at or below this many queries
-    bool kmerDupAttr = false;                      // k_kmer_dup_stream may use more than 64 KB of dynamic LDS on this context's device (keys of more than 24 k target ids)
+    bool kmerDupAttr = false;                      // k_kmer_dup_stream may use more than 60 KB of dynamic LDS on this context's device (its table is one byte per target id of a key)
     int kmerBatchOk = 0;                           // batches that succeeded in a row under the current cap (it is relaxed after four)
     uint64_t kmerCounts[4] = {0, 0, 0, 0};   // last batch: k-mer lists probed, index hits, double-diagonal candidates, elements handed to the host
 
@@ -100,7 +103,6 @@ struct fsgpu_ctx {
     PinBuf hMqPssm, hMqRec, hMqMeta, hMqOutId, hMqOutScore, hMqIdent;
     int mqLaunches = 0, mqQueries = 0;          // scan kernel launches / queries of the last batch
     double mqScanMs = -1.0;                     // >= 0: scan time of the last multi-query call incl. its row-tiled queries
-    hipEvent_t swChainEv = nullptr;             // FSGPU_SW_EXCLUSIVE=1: recorded behind a k_sw3 pass that took its turn in the scan chain
     hipEvent_t scanDoneEv = nullptr;            // recorded after the last scan launch of a batch (chained through DbStore::lastScanDone)
     uint64_t mqScoreStride = 0;
     std::vector<int> mqSlot;                    // query index of the last call -> slice of mqScores (-1: went through the single-query path)
@@ -108,9 +110,8 @@ struct fsgpu_ctx {
     // sw scratch
     hipStream_t swHi = nullptr;                 // highest-priority stream of the batch SW (fsgpu_sw_multi_dir_c); null: ctx->stream
     int swHiPrio = 0;
-    std::vector<uint32_t> swCuMask;             // FSGPU_SW_CUS: the CU mask of the batch SW's streams (empty: priorities)
     static constexpr int kSwAux = 12;           // side streams: register-class groups (and, in the one-submission form, directions) of a multi-query launch overlap their tails
-    hipStream_t swAux[kSwAux] = {};
+    hipStream_t swAux[kSwAux] = {};             // created by swFork: of swHiPrio when the context has swHi, plain otherwise
     hipEvent_t swAuxEv[kSwAux + 1] = {};        // [kSwAux]: the fork event
     DevBuf img, tids, res0, res1, border0, border1, keys;
     // per-pass accounting of the last fsgpu_sw_multi_dir calls (fsgpu_sw_last_passes): k_sw2 launches only (single-tile queries),
@@ -156,9 +157,8 @@ struct fsgpu_ctx {
         }                                                                                              \
     } while (0)
 
-// Wait for the context stream by polling: hipStreamSynchronize from a non-main host thread falls back to a blocking
-// wait that costs ~0.2 ms per call on this stack, more than the kernels it waits for.
-// Wait for the context's stream.  Poll for a short while (a scan finishes in a few hundred microseconds and the caller
+// Wait for a stream of the context by polling: hipStreamSynchronize from a non-main host thread falls back to a blocking
+// wait that costs ~0.2 ms per call on this stack, more than the kernels it waits for.  Poll for a short while (a scan finishes in a few hundred microseconds and the caller
 // wants the result right away), then back off to short sleeps: a host thread that waits must not burn a core -- several
 // feeder threads per GPU times eight GPUs exceeds the CPU quota of a container long before it exceeds the GPUs.
 // FSGPU_SPIN_US overrides the polling window (microseconds, default 40; 0 = sleep immediately).
@@ -200,3 +200,69 @@ inline int ensure(fsgpu_ctx *ctx, DevBuf &b, size_t bytes) {
     return FSGPU_OK;
 }
 
+// several buffers at once: {buffer, bytes} pairs
+struct DevReq { DevBuf &b; size_t bytes; };
+struct PinReq { PinBuf &b; size_t bytes; };
+inline int ensureAll(fsgpu_ctx *ctx, std::initializer_list<DevReq> reqs) {
+    for (const DevReq &r : reqs) { const int rc = ensure(ctx, r.b, r.bytes); if (rc != FSGPU_OK) return rc; }
+    return FSGPU_OK;
+}
+inline int ensurePinnedAll(fsgpu_ctx *ctx, std::initializer_list<PinReq> reqs) {
+    for (const PinReq &r : reqs) { const int rc = ensurePinned(ctx, r.b, r.bytes); if (rc != FSGPU_OK) return rc; }
+    return FSGPU_OK;
+}
+
+inline void freeDb(fsgpu_ctx *ctx) { ctx->db.reset(); ctx->kidx.reset(); }
+
+inline uint64_t hashWords(uint64_t h, const void *p, size_t bytes) {
+    const unsigned char *c = (const unsigned char *) p;
+    size_t i = 0;
+    for (; i + 8 <= bytes; i += 8) { uint64_t w; memcpy(&w, c + i, 8); h = (h ^ w) * 0x9E3779B97F4A7C15ull; h ^= h >> 29; }
+    for (; i < bytes; i++) h = (h ^ c[i]) * 0x100000001B3ull;
+    return h;
+}
+
+// ---- shared by the two multi-query SW entry points (fsgpu_sw_multi_dir: profiles, fsgpu_sw_multi_dir_c / fsgpu_sw_multi_c: compact queries) ----
+// what a call needs whatever its queries are: a database, gap costs the kernels reproduce, no single-query batch in flight
+inline int swCheckCall(fsgpu_ctx *ctx, int gapOpen, int gapExtend) {
+    if (!ctx->db || ctx->db->n == 0) { ctx->err = "no database loaded"; return FSGPU_E_NODB; }
+    if (!(gapOpen > gapExtend && gapExtend >= 0 && gapOpen < 32768)) {
+        ctx->err = "device SW requires gapOpen > gapExtend >= 0 (the striped reference kernel's lazy-F shortcut is only reproduced for that case)";
+        return FSGPU_E_UNSUPPORTED;
+    }
+    if (ctx->sw.pending) { ctx->err = "previous SW batch not finished"; return FSGPU_E_ARG; }
+    return FSGPU_OK;
+}
+// the pairs of one query: n target ids, of which sel[0 .. ns) run in this call (haveSel false: all of them, ns = n)
+inline int swCheckPairs(fsgpu_ctx *ctx, const char *who, const uint32_t *targetIds, int n, bool haveSel, const int32_t *sel, int ns) {
+    if (ns < 0 || ns > n || (haveSel && ns > 0 && !sel)) { ctx->err = std::string(who) + ": bad selection"; return FSGPU_E_ARG; }
+    for (int k = 0; k < n; k++) if (targetIds[k] >= ctx->db->n) { ctx->err = "target id out of range"; return FSGPU_E_ARG; }
+    if (haveSel) for (int k = 0; k < ns; k++) if (sel[k] < 0 || sel[k] >= n) { ctx->err = std::string(who) + ": selection index out of range"; return FSGPU_E_ARG; }
+    return FSGPU_OK;
+}
+// launch order of those pairs: perm[0 .. ns) = indices into targetIds, longest target first (neighbours share a wave); sel == nullptr: pairs 0 .. ns
+inline void swSortLongestFirst(const std::vector<int32_t> &len, const uint32_t *targetIds, const int32_t *sel, int ns, std::vector<uint64_t> &lkey, uint32_t *perm) {
+    lkey.resize(ns);
+    for (int k = 0; k < ns; k++) { const int j = sel ? sel[k] : k; lkey[k] = ((uint64_t) (0xFFFFFF - len[targetIds[j]]) << 32) | (uint32_t) j; }
+    std::sort(lkey.begin(), lkey.end());
+    for (int k = 0; k < ns; k++) perm[k] = (uint32_t) lkey[k];
+}
+// Side streams of one SW submission: its launch groups run on `from` and on swAux[1 .. nStreams), so their long-target tails overlap.  swFork creates what is
+// missing (of swHiPrio when the context has swHi, plain otherwise) and makes them wait for what `from` holds so far (the inputs); swJoin makes `from` wait for them.
+inline int swFork(fsgpu_ctx *ctx, hipStream_t from, size_t nStreams) {
+    if (nStreams <= 1) return FSGPU_OK;
+    hipEvent_t &forkEv = ctx->swAuxEv[fsgpu_ctx::kSwAux];
+    if (!forkEv) for (int i = 0; i <= fsgpu_ctx::kSwAux; i++) HIPCHK(hipEventCreateWithFlags(&ctx->swAuxEv[i], hipEventDisableTiming));
+    for (size_t k = 1; k < nStreams; k++) {
+        if (ctx->swAux[k]) continue;
+        if (ctx->swHi) HIPCHK(hipStreamCreateWithPriority(&ctx->swAux[k], hipStreamNonBlocking, ctx->swHiPrio));
+        else HIPCHK(hipStreamCreateWithFlags(&ctx->swAux[k], hipStreamNonBlocking));
+    }
+    HIPCHK(hipEventRecord(forkEv, from));
+    for (size_t k = 1; k < nStreams; k++) HIPCHK(hipStreamWaitEvent(ctx->swAux[k], forkEv, 0));
+    return FSGPU_OK;
+}
+inline int swJoin(fsgpu_ctx *ctx, hipStream_t from, size_t nStreams) {
+    for (size_t k = 1; k < nStreams; k++) { HIPCHK(hipEventRecord(ctx->swAuxEv[k], ctx->swAux[k])); HIPCHK(hipStreamWaitEvent(from, ctx->swAuxEv[k], 0)); }
+    return FSGPU_OK;
+}

@@ -769,23 +769,6 @@ int fshost_search_align_batch(fshost_search *s, int nq, const uint8_t *const *qA
         total += (size_t) n[i];
     }
     const int8_t *m3 = s->mat3Di.tiny.data(), *mA = useAA ? s->matAA.tiny.data() : nullptr;
-    // FSGPU_SW_PROFILES=1: the profile-based device entry (word profiles built here, LDS images built on the host, k_sw2) instead of the
-    // compact one -- kept for A/B measurements of the two device paths (tools/sw2_probe.py)
-    static const bool viaProfiles = [] { const char *e = getenv("FSGPU_SW_PROFILES"); return e && *e && *e != '0'; }();
-    std::vector<fsgpu_sw_query> pq;
-    if (viaProfiles) {
-        pq.resize(nq);
-        for (int i = 0; i < nq; i++) {
-            materializeProfiles(s, aq[i]);
-            pq[i].pAA_fwd = useAA ? aq[i].pAAf.data() : nullptr; pq[i].p3Di_fwd = aq[i].p3f.data();
-            pq[i].pAA_rev = useAA ? aq[i].pAAr.data() : nullptr; pq[i].p3Di_rev = aq[i].p3r.data();
-            pq[i].L = L[i]; pq[i].n = n[i]; pq[i].targetIds = targetIds[i];
-        }
-    }
-    auto pass = [&](int dir, const int32_t *const *sel, const int32_t *nsel, fsgpu_swres *out) {
-        return viaProfiles ? fsgpu_sw_multi_dir(s->ctx, pq.data(), nq, par.gapOpen, par.gapExtend, dir, sel, nsel, out)
-                           : fsgpu_sw_multi_dir_c(s->ctx, m3, mA, dq.data(), nq, par.gapOpen, par.gapExtend, dir, sel, nsel, out);
-    };
     s->fwd.resize(total); s->rev.assign(total, fsgpu_swres{0, 0, 0, 0});
     const double t1 = nowSec();
     // A small batch (the all-vs-all steps: a few thousand pairs per call) is bound by round trips, not by DP cells: both directions of
@@ -793,7 +776,7 @@ int fshost_search_align_batch(fshost_search *s, int nq, const uint8_t *const *qA
     // score passes the gates (3-16 % of a search's hit lists).  FSGPU_SW_ONEPASS_PAIRS overrides the limit (0 = never).
     static const size_t onePassPairs = [] { const char *e = getenv("FSGPU_SW_ONEPASS_PAIRS"); return e ? (size_t) atoll(e) : (size_t) 16384; }();
     int rc;
-    if (!viaProfiles && total > 0 && total <= onePassPairs) {
+    if (total > 0 && total <= onePassPairs) {
         rc = fsgpu_sw_multi_c(s->ctx, m3, mA, dq.data(), nq, par.gapOpen, par.gapExtend, s->fwd.data(), s->rev.data());
         if (rc != FSGPU_OK) { s->err = fsgpu_last_error(s->ctx); return rc; }
         size_t b = 0, any = 0;
@@ -808,7 +791,7 @@ int fshost_search_align_batch(fshost_search *s, int nq, const uint8_t *const *qA
         }
         s->stats[7] = (double) any;
     } else {
-    rc = pass(0, nullptr, nullptr, s->fwd.data());
+    rc = fsgpu_sw_multi_dir_c(s->ctx, m3, mA, dq.data(), nq, par.gapOpen, par.gapExtend, 0, nullptr, nullptr, s->fwd.data());
     if (rc != FSGPU_OK) { s->err = fsgpu_last_error(s->ctx); return rc; }
     {
         std::vector<std::vector<int32_t>> sel(nq);
@@ -826,7 +809,7 @@ int fshost_search_align_batch(fshost_search *s, int nq, const uint8_t *const *qA
         }
         s->stats[7] = (double) any;
         if (any) {
-            rc = pass(1, selp.data(), nsel.data(), s->rev.data());
+            rc = fsgpu_sw_multi_dir_c(s->ctx, m3, mA, dq.data(), nq, par.gapOpen, par.gapExtend, 1, selp.data(), nsel.data(), s->rev.data());
             if (rc != FSGPU_OK) { s->err = fsgpu_last_error(s->ctx); return rc; }
         }
     }

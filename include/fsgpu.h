@@ -353,7 +353,7 @@ void fsgpu_kmer_last_counts(const fsgpu_ctx *ctx, uint64_t *out4);
 int fsgpu_kmer_batch_hint(const fsgpu_ctx *ctx);
 /* Accounting of the last batch's hit-stream partition (round 6: one order-preserving scatter into (query, key) runs, a key = a run of blocks
  * of 1024 target ids): [1] = [4] (query, databaseHits chunk, key) runs walked by the duplicate stage, [3] tiles of the scatter, [5] coarse keys
- * of the level the batch used, [6] target ids of its widest key (16 bits of LDS each in k_kmer_dup_stream); [0] = [2] = 0. */
+ * of the level the batch used, [6] target ids of its widest key (one byte of LDS each in k_kmer_dup_stream); [0] = [2] = 0. */
 void fsgpu_kmer_last_segments(const fsgpu_ctx *ctx, uint32_t *out7);
 /* The coarse keys of that partition (host-only planning, also used by the index build): consecutive blocks of 1024 target ids joined into keys.
  * blocksPerKey = 1..64: that many blocks per key; 0: about 128 keys of equal residue count, none longer than twice the average number of blocks

@@ -41,7 +41,7 @@ LENGTHS = [1, 20, 33, 64, 65, 97, 129, 161, 193, 225, 257, 289, 321, 350, 353, 3
 PAIRS = [1, 2, 3, 4, 5, 7, 9, 16, 17, 33, 64, 31, 120, 250, 6, 11, 13, 66, 15, 130, 1, 3, 5, 8, 19, 34, 4, 2, 70, 9]
 
 
-# which lanes-per-pair shape a pair takes is a launch decision (fsgpu.hip sw3MultiImpl): the automatic rule (lists of <= 16 pairs with 64 lanes, the
+# which lanes-per-pair shape a pair takes is a launch decision (fsgpu_sw3_multi.hip sw3SortAndSplit): the automatic rule (lists of <= 16 pairs with 64 lanes, the
 # 16-lane shape only in calls of >= 100 000 pairs), the 16-lane shape forced for targets of up to 512 / 896 columns, and the short-list rule off --
 # every (shape, rows-per-lane) class must give the per-pair kernel's records
 SHAPES = {"auto": {}, "mid512": {"FSGPU_SW3_MID": "512"}, "mid896_noshort": {"FSGPU_SW3_MID": "896", "FSGPU_SW3_SHORT": "0"},

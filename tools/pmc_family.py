@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Summarise rocprofv3 --pmc passes per kernel FAMILY (template arguments stripped): dispatches and counter totals, plus
 derived per-query figures for the scan kernel (a multi-query k_gapless launch runs grid / (512 workgroups x 256 threads)
-queries: 2 workgroups per CU x 256 CUs per query, fsgpu.hip::launchGapless; --wg-per-query N overrides).
+queries: 2 workgroups per CU x 256 CUs per query, fsgpu_gapless.hip::launchGapless; --wg-per-query N overrides).
 --from-first NAME drops every dispatch before the first one of kernel NAME (per pass): e.g. the index build in front of a k-mer batch.
 usage: pmc_family.py <dir-with-counter_collection.csv> ... [--json out.json] [--from-first k_kmer_count]"""
 import collections
