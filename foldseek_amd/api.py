@@ -45,6 +45,22 @@ class KmerQuery(C.Structure):
 KMER_HIT_DT = np.dtype([("id", np.uint32), ("score", np.int32), ("diag", np.uint16), ("pad", np.uint16)])
 
 
+class BtQuery(C.Structure):
+    """fsgpu_bt_query"""
+    _fields_ = [("qAA", C.c_void_p), ("q3Di", C.c_void_p), ("cbAA", C.c_void_p), ("cbSS", C.c_void_p), ("L", C.c_int32), ("reserved", C.c_int32)]
+
+
+class BtTask(C.Structure):
+    """fsgpu_bt_task"""
+    _fields_ = [("query", C.c_uint32), ("target", C.c_uint32), ("qEnd", C.c_int32), ("dbEnd", C.c_int32), ("score", C.c_int32)]
+
+
+class BtRes(C.Structure):
+    """fsgpu_bt_res"""
+    _fields_ = [("status", C.c_int32), ("qStart", C.c_int32), ("dbStart", C.c_int32), ("identicalAA", C.c_int32), ("btLen", C.c_int32),
+                ("blockSizes", C.c_int32), ("btOff", C.c_uint64)]
+
+
 class FsgpuError(RuntimeError):
     pass
 
@@ -68,6 +84,9 @@ def lib():
         "fsgpu_clone": (i32, [vp, C.POINTER(vp)]),
         "fsgpu_device": (i32, [vp]),
         "fsgpu_device_count": (i32, []),
+        "fsgpu_live_devices": (i32, []),
+        "fsgpu_block_backtrace": (i32, [vp, vp, vp, vp, vp, C.POINTER(BtQuery), i32, C.POINTER(BtTask), i32, i32, i32, C.POINTER(BtRes), C.POINTER(C.c_void_p)]),
+        "fsgpu_block_backtrace_footprint": (i32, [vp, i32]),
         "fsgpu_gapless_plan_items": (i64, [vp, C.c_uint32, i32, f64, vp, u64, vp]),
         "fsgpu_db_broadcast": (i32, [vp, C.POINTER(vp), i32, C.POINTER(i32)]),
         "fsgpu_rccl_selfcheck": (i32, [vp]),
@@ -158,7 +177,7 @@ def exported_symbols():
     return ["fsgpu_create", "fsgpu_destroy", "fsgpu_last_error", "fsgpu_device", "fsgpu_stream", "fsgpu_db_load",
             "fsgpu_db_adopt_device", "fsgpu_db_size", "fsgpu_db_residues", "fsgpu_gapless_scan", "fsgpu_gapless_scores",
             "fsgpu_gapless_launch", "fsgpu_gapless_finish", "fsgpu_sw_batch", "fsgpu_sw_multi", "fsgpu_sw_multi_dir", "fsgpu_sw_multi_dir_c", "fsgpu_sw_multi_c", "fsgpu_sw_launch", "fsgpu_sw_finish",
-            "fsgpu_db_broadcast", "fsgpu_rccl_selfcheck", "fsgpu_device_count", "fsgpu_live_devices", "fsgpu_gapless_plan_items", "fsgpu_block_backtrace_footprint",
+            "fsgpu_db_broadcast", "fsgpu_rccl_selfcheck", "fsgpu_device_count", "fsgpu_live_devices", "fsgpu_gapless_plan_items", "fsgpu_block_backtrace", "fsgpu_block_backtrace_footprint",
             "fsgpu_last_kernel_ms", "fsgpu_sw_last_passes", "fsgpu_kmer_index_build", "fsgpu_kmer_index_entries", "fsgpu_kmer_search",
             "fsgpu_kmer_index_copy", "fsgpu_kmer_row_copy", "fsgpu_kmer_last_counts", "fsgpu_kmer_last_segments", "fsgpu_kmer_plan_coarse", "fsgpu_kmer_batch_hint"]
 
@@ -529,6 +548,43 @@ class Context:
         self._chk(lib().fsgpu_sw_batch(self.h, _ptr(pAAf), _ptr(p3f), _ptr(pAAr), _ptr(p3r), p3f.shape[1], _ptr(t), len(t),
                                        gap_open, gap_extend, _ptr(fwd), _ptr(rev)), "fsgpu_sw_batch")
         return fwd, rev
+
+    def block_backtrace(self, tblAA, tbl3Di, letAA, let3Di, queries, tasks, gap_open=10, gap_extend=1):
+        """fsgpu_block_backtrace called directly: start position + backtrace of accepted hits by the device block aligner, nothing recomputed on the
+        host.  tblAA / tbl3Di: int8 [27, 32] letter-indexed tables, letAA / let3Di: uint8 [21] code -> letter - 'A'; queries: list of
+        (qAA, q3Di, cbAA, cbSS) (codes 0..20 and the int8 composition bias arrays); tasks: list of (query, target, qEnd, dbEnd, score).
+        Returns one dict per task: status (1 answered, 2 SW score not reproduced, 0 handed back), qStart, dbStart, identicalAA, blockSizes and the
+        backtrace string, copied out of the context's buffer before the next call can overwrite it."""
+        tA, t3 = np.ascontiguousarray(tblAA, np.int8), np.ascontiguousarray(tbl3Di, np.int8)
+        lA, l3 = np.ascontiguousarray(letAA, np.uint8), np.ascontiguousarray(let3Di, np.uint8)
+        if tA.size != 27 * 32 or t3.size != 27 * 32 or lA.size != 21 or l3.size != 21:
+            raise FsgpuError("block_backtrace: tables must be int8 [27, 32], letter maps uint8 [21]")
+        nq, nt = len(queries), len(tasks)
+        qs, keep = (BtQuery * max(nq, 1))(), []
+        for i, (qa, q3, ca, cs) in enumerate(queries):
+            bufs = (np.ascontiguousarray(qa, np.uint8), np.ascontiguousarray(q3, np.uint8), np.ascontiguousarray(ca, np.int8), np.ascontiguousarray(cs, np.int8))
+            if not (len(bufs[0]) == len(bufs[1]) == len(bufs[2]) == len(bufs[3])):
+                raise FsgpuError(f"block_backtrace: query {i}: sequences and bias arrays differ in length")
+            keep.append(bufs)
+            qs[i].qAA, qs[i].q3Di, qs[i].cbAA, qs[i].cbSS = [b.ctypes.data for b in bufs]
+            qs[i].L, qs[i].reserved = len(bufs[0]), 0
+        ts = (BtTask * max(nt, 1))()
+        for k, (q, t, qe, de, sc) in enumerate(tasks):
+            ts[k].query, ts[k].target, ts[k].qEnd, ts[k].dbEnd, ts[k].score = int(q), int(t), int(qe), int(de), int(sc)
+        res = (BtRes * max(nt, 1))()
+        base = C.c_void_p()
+        self._chk(lib().fsgpu_block_backtrace(self.h, _ptr(tA), _ptr(t3), _ptr(lA), _ptr(l3), qs, nq, ts, nt, int(gap_open), int(gap_extend), res,
+                                              C.byref(base)), "fsgpu_block_backtrace")
+        out = []
+        for k in range(nt):
+            r = res[k]
+            bt = C.string_at(base.value + r.btOff, r.btLen).decode() if r.status == 1 and r.btLen > 0 else ""
+            out.append(dict(status=r.status, qStart=r.qStart, dbStart=r.dbStart, identicalAA=r.identicalAA, blockSizes=r.blockSizes, backtrace=bt))
+        return out
+
+    def block_backtrace_footprint(self, workgroups_per_cu):
+        """workgroups of the block aligner per compute unit for the following block_backtrace calls (0: the default)"""
+        self._chk(lib().fsgpu_block_backtrace_footprint(self.h, int(workgroups_per_cu)), "fsgpu_block_backtrace_footprint")
 
     def kernel_ms(self, which):
         return lib().fsgpu_last_kernel_ms(self.h, which)

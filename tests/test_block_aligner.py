@@ -557,6 +557,7 @@ def test_trajectory_model_reproduces_the_kat_answers():
     boundary cases and (round 5) 189 call sequences of up to 180 residues taken from tools/ba_model_sweep.py runs on which a RARE decision fired (x-drop
     threshold met exactly / missed by one, second bad x-drop step, shrink with equality, a Grow that grew again; names swp<seed>_<boundaries>_...): every line of the restatement's frozen answers (score, end cell, CIGAR, block sizes tried)"""
     import os
+    import sys
     from ba_model import BlockModel
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     kat = os.path.join(root, "oracle", "ba_kat")
@@ -574,6 +575,9 @@ def test_trajectory_model_reproduces_the_kat_answers():
 
     mAA, m3 = load(os.path.join(kat, "mat_aa.txt")), load(os.path.join(kat, "mat_3di.txt"))
     want = [ln.rstrip("\n").split("\t") for ln in open(os.path.join(kat, "ours_v3.txt"))]
+    sys.path.insert(0, kat)
+    import make_long_cases as long_cases
+    classes = dict((f[0], f[1:]) for f in (ln.split() for ln in open(os.path.join(kat, "cases_classes.txt"))))
     k = 0
     for line in open(os.path.join(kat, "cases.txt")):
         if not line.strip() or line[0] == "#":
@@ -584,13 +588,16 @@ def test_trajectory_model_reproduces_the_kat_answers():
             qa, q3, qb, ta, t3 = f[4:9]
             target = int(name.split("@")[1])
             qbias = ([0] * len(qa) if qb == "-" else [int(x) for x in qb.split(",")] + [0] * len(qa))[:len(qa)]
-            res, sizes, ms = (-10 ** 9, 0, 0), [], 32
+            res, sizes, ms, placed = (-10 ** 9, 0, 0), [], 32, []
             while ms <= 4096 and res[0] < target:
                 M = BlockModel(qa, ta, mAA, -go, -ge, ms, 4096, x_drop=-(ms * (-ge) + (-go)), q_bias=qbias, r_bias=[0] * len(ta), score2=m3, q2=q3, r2=t3)
                 res = M.align()
                 sizes.append(f"{ms}:{res[0]}")
+                placed.append((ms, res[0], max(step[3] for step in M.steps)))
                 ms *= 2
             got = [name, str(res[0]), str(res[1]), str(res[2]), M.trace.cigar(res[1], res[2]) or "-", ",".join(sizes)]
+            # what the device aligner must do with the case (tests/test_btrace_model_gpu.py), from the model's block sizes: the frozen verdict is this one
+            assert classes[name] == [long_cases.classify(placed, target), str(max(x[2] for x in placed))], (name, placed)
         else:
             rest = f[4:]
             sc = mAA

@@ -1,7 +1,10 @@
 """Device block-aligner backtrace (k_btrace.hpp, fsgpu_block_backtrace; SURVEY row a16 on the MI355X) against the host restatement (host/block_aligner.cpp,
 which the CPU suite holds to the crate's known answers and to the independent trajectory model): the SAME align_batch call with the device path on and
 off must return identical records -- start positions, alignment length, sequence identity, backtrace strings -- for every accepted hit, and the device
-must have answered most of them itself (hits whose block wants to grow beyond 128 rows are handed back to the host path by design)."""
+must have answered most of them itself (hits whose block wants to grow beyond 128 rows are handed back to the host path by design).
+Both sides of these comparisons descend from the same reading of the crate, and the host path recomputes whatever the kernel hands back: where the kernel
+meets something OTHER than the restatement -- the independent model's frozen answers, through a direct fsgpu_block_backtrace call with exact statuses -- is
+tests/test_btrace_model_gpu.py."""
 import os
 
 import numpy as np
@@ -33,7 +36,7 @@ def _run(world, atype, go, ge, device):
     os.environ.pop("FSGPU_DEVICE_BACKTRACE", None)
     os.environ.pop("FSGPU_BT_SHARE_MIN", None)
     if device is None:
-        os.environ["FSGPU_DEVICE_BACKTRACE"] = "2"        # host pool and device share the batch's list (the default on hosts with <= 4 cores; from 1024 hits on, here from 128)
+        os.environ["FSGPU_DEVICE_BACKTRACE"] = "2"        # host pool and device share the batch's list (opt-in: the default at 4 cores or fewer is mode 1; from 1024 hits on, here from 128)
         os.environ["FSGPU_BT_SHARE_MIN"] = "128"
     else:
         os.environ["FSGPU_DEVICE_BACKTRACE"] = "1" if device else "0"
@@ -53,7 +56,7 @@ def _run(world, atype, go, ge, device):
 
 @pytest.mark.parametrize("atype", [0, 2])
 def test_shared_backtrace_equals_host_backtrace(world, atype):
-    """FSGPU_DEVICE_BACKTRACE=2 (the default where cores are few): the pool's threads take hits from the front of the batch's list, the device aligner chunks from its back;
+    """FSGPU_DEVICE_BACKTRACE=2 (opt-in; where cores are few the default is mode 1, the device alone): the pool's threads take hits from the front of the batch's list, the device aligner chunks from its back;
     both must have answered hits, and the records must be the host aligner's"""
     rs, bs, (on_dev, total) = _run(world, atype, 10, 1, None)
     rh, bh, (on_dev_h, total_h) = _run(world, atype, 10, 1, False)
