@@ -61,6 +61,17 @@ class BtRes(C.Structure):
                 ("blockSizes", C.c_int32), ("btOff", C.c_uint64)]
 
 
+class LddtQuery(C.Structure):
+    """fsgpu_lddt_query"""
+    _fields_ = [("ca", C.c_void_p), ("L", C.c_int32), ("reserved", C.c_int32)]
+
+
+class LddtTask(C.Structure):
+    """fsgpu_lddt_task"""
+    _fields_ = [("query", C.c_uint32), ("tLen", C.c_int32), ("tOff", C.c_uint64), ("qStart", C.c_int32), ("dbStart", C.c_int32),
+                ("btOff", C.c_uint64), ("btLen", C.c_uint32), ("reserved", C.c_uint32), ("outOff", C.c_uint64)]
+
+
 class FsgpuError(RuntimeError):
     pass
 
@@ -87,6 +98,11 @@ def lib():
         "fsgpu_live_devices": (i32, []),
         "fsgpu_block_backtrace": (i32, [vp, vp, vp, vp, vp, C.POINTER(BtQuery), i32, C.POINTER(BtTask), i32, i32, i32, C.POINTER(BtRes), C.POINTER(C.c_void_p)]),
         "fsgpu_block_backtrace_footprint": (i32, [vp, i32]),
+        "fsgpu_lddt_batch": (i32, [vp, C.POINTER(LddtQuery), i32, C.POINTER(LddtTask), i32, vp, u64, vp, u64, vp, vp, u64]),
+        "fshost_ca_decode": (i32, [vp, C.c_size_t, i32, vp]),
+        "fshost_lddt_average": (f64, [vp, i32, C.POINTER(i32)]),
+        "fshost_search_bind_ca": (i32, [vp, f32, vp, vp, vp]),
+        "fshost_search_set_query_ca": (i32, [vp, i32, vp, vp]),
         "fsgpu_gapless_plan_items": (i64, [vp, C.c_uint32, i32, f64, vp, u64, vp]),
         "fsgpu_db_broadcast": (i32, [vp, C.POINTER(vp), i32, C.POINTER(i32)]),
         "fsgpu_rccl_selfcheck": (i32, [vp]),
@@ -178,7 +194,7 @@ def exported_symbols():
             "fsgpu_db_adopt_device", "fsgpu_db_size", "fsgpu_db_residues", "fsgpu_gapless_scan", "fsgpu_gapless_scores",
             "fsgpu_gapless_launch", "fsgpu_gapless_finish", "fsgpu_sw_batch", "fsgpu_sw_multi", "fsgpu_sw_multi_dir", "fsgpu_sw_multi_dir_c", "fsgpu_sw_multi_c", "fsgpu_sw_launch", "fsgpu_sw_finish",
             "fsgpu_db_broadcast", "fsgpu_rccl_selfcheck", "fsgpu_device_count", "fsgpu_live_devices", "fsgpu_gapless_plan_items", "fsgpu_block_backtrace", "fsgpu_block_backtrace_footprint",
-            "fsgpu_last_kernel_ms", "fsgpu_sw_last_passes", "fsgpu_kmer_index_build", "fsgpu_kmer_index_entries", "fsgpu_kmer_search",
+            "fsgpu_lddt_batch", "fsgpu_last_kernel_ms", "fsgpu_sw_last_passes", "fsgpu_kmer_index_build", "fsgpu_kmer_index_entries", "fsgpu_kmer_search",
             "fsgpu_kmer_index_copy", "fsgpu_kmer_row_copy", "fsgpu_kmer_last_counts", "fsgpu_kmer_last_segments", "fsgpu_kmer_plan_coarse", "fsgpu_kmer_batch_hint"]
 
 
@@ -582,6 +598,35 @@ class Context:
             out.append(dict(status=r.status, qStart=r.qStart, dbStart=r.dbStart, identicalAA=r.identicalAA, blockSizes=r.blockSizes, backtrace=bt))
         return out
 
+    def lddt_batch(self, queries, targets, tasks):
+        """fsgpu_lddt_batch called directly: the reference's per-residue LDDT values of a batch of hits.  queries / targets: lists of float32
+        arrays [3, L] (x, y, z rows, what ca_decode returns); tasks: list of (query, target, qStart, dbStart, backtrace string).  Returns one
+        (alignLength, float32 array of alignLength per-column values) per task; a NaN marks a column the average skips (lddt_average)."""
+        nq, nt = len(queries), len(tasks)
+        qs, keep = (LddtQuery * max(nq, 1))(), []
+        for i, q in enumerate(queries):
+            q = np.ascontiguousarray(q, np.float32)
+            if q.ndim != 2 or q.shape[0] != 3:
+                raise FsgpuError(f"lddt_batch: query {i}: coordinates must be float32 [3, L]")
+            keep.append(q)
+            qs[i].ca, qs[i].L, qs[i].reserved = q.ctypes.data, q.shape[1], 0
+        tl = [np.ascontiguousarray(t, np.float32) for t in targets]
+        toff = np.concatenate([[0], np.cumsum([t.size for t in tl])]).astype(np.int64)
+        tc = np.concatenate([t.reshape(-1) for t in tl]) if tl else np.zeros(0, np.float32)
+        bts = [str(t[4]).encode() for t in tasks]
+        ts = (LddtTask * max(nt, 1))()
+        boff = ooff = 0
+        for k, (q, t, qs0, ds0, _) in enumerate(tasks):
+            ts[k].query, ts[k].tLen, ts[k].tOff, ts[k].qStart, ts[k].dbStart = int(q), tl[int(t)].shape[1], int(toff[int(t)]), int(qs0), int(ds0)
+            ts[k].btOff, ts[k].btLen, ts[k].reserved, ts[k].outOff = boff, len(bts[k]), 0, ooff
+            boff += len(bts[k])
+            ooff += bts[k].count(b"M")
+        bt = np.frombuffer(b"".join(bts), np.uint8) if boff else np.zeros(0, np.uint8)
+        aln = np.full(max(nt, 1), -1, np.int32)
+        out = np.full(max(ooff, 1), -1.0, np.float32)
+        self._chk(lib().fsgpu_lddt_batch(self.h, qs, nq, ts, nt, _ptr(tc), tc.size, _ptr(bt), bt.size, _ptr(aln), _ptr(out), ooff), "fsgpu_lddt_batch")
+        return [(int(aln[k]), out[ts[k].outOff:ts[k].outOff + max(int(aln[k]), 0)].copy()) for k in range(nt)]
+
     def block_backtrace_footprint(self, workgroups_per_cu):
         """workgroups of the block aligner per compute unit for the following block_backtrace calls (0: the default)"""
         self._chk(lib().fsgpu_block_backtrace_footprint(self.h, int(workgroups_per_cu)), "fsgpu_block_backtrace_footprint")
@@ -789,3 +834,21 @@ def format_prefilter_hit(key, score, diagonal=0):
     buf = C.create_string_buffer(64)
     n = lib().fshost_format_prefilter_hit(buf, key, score, diagonal)
     return buf.raw[:n].decode()
+
+
+def ca_decode(entry, L):
+    """fshost_ca_decode (Coordinate16::read): a <db>_ca entry (bytes, as stored: terminator included or not) of a chain of L residues ->
+    float32 [3, L] (x, y, z rows)"""
+    buf = np.frombuffer(bytes(entry), np.uint8)
+    out = np.zeros((3, int(L)), np.float32)
+    if lib().fshost_ca_decode(_ptr(buf), len(buf), int(L), _ptr(out)) != 0:
+        raise FsgpuError(f"ca_decode: an entry of {len(buf)} bytes is too short for {L} residues")
+    return out
+
+
+def lddt_average(cols):
+    """fshost_lddt_average (LDDTScoreResult, LDDT.h:102-119): (avgLddtScore, scoreLength) of the per-column values of one hit"""
+    c = np.ascontiguousarray(cols, np.float32)
+    n = C.c_int(0)
+    avg = lib().fshost_lddt_average(_ptr(c), len(c), C.byref(n))
+    return avg, n.value

@@ -87,7 +87,7 @@ void fsgpu_destroy(fsgpu_ctx *ctx) {
     DevBuf *bufs[] = {&ctx->gBorder0, &ctx->gBorder1, &ctx->scoreAcc, &ctx->pssm, &ctx->scores, &ctx->chunkHist, &ctx->baseGt, &ctx->baseTie, &ctx->outId, &ctx->outScore,
                       &ctx->img, &ctx->tids, &ctx->res0, &ctx->res1, &ctx->border0, &ctx->border1, &ctx->keys, &ctx->lbuf, &ctx->lres,
                       &ctx->ovAA, &ctx->ovSS, &ctx->ovOff, &ctx->ovLen, &ctx->s3img, &ctx->s3pass, &ctx->s3build, &ctx->s3res,
-                      &ctx->btSeq, &ctx->btTrace, &ctx->btBlocks, &ctx->btOut, &ctx->btIn,
+                      &ctx->btSeq, &ctx->btTrace, &ctx->btBlocks, &ctx->btOut, &ctx->btIn, &ctx->ldIn, &ctx->ldNorm, &ctx->ldCols, &ctx->ldOut,
                       &ctx->mqPssm, &ctx->mqScores, &ctx->mqQueues, &ctx->mqRec, &ctx->mqHist, &ctx->mqBaseGt, &ctx->mqBaseTie, &ctx->mqMeta,
                       &ctx->mqOutId, &ctx->mqOutScore, &ctx->mqIdent};
     for (DevBuf *b : bufs) if (b->p) hipFree(b->p);
@@ -95,7 +95,8 @@ void fsgpu_destroy(fsgpu_ctx *ctx) {
     hipHostFree(ctx->hMeta); hipHostFree(ctx->hOutId.p); hipHostFree(ctx->hOutScore.p);
     hipHostFree(ctx->hRes0.p); hipHostFree(ctx->hRes1.p); hipHostFree(ctx->hLbuf.p); hipHostFree(ctx->hLres.p);
     hipHostFree(ctx->hS3pass.p); hipHostFree(ctx->hS3build.p); hipHostFree(ctx->hS3res.p);
-    hipHostFree(ctx->hBtIn.p); hipHostFree(ctx->hBtOut.p);
+    hipHostFree(ctx->hBtIn.p); hipHostFree(ctx->hBtOut.p); hipHostFree(ctx->hLdIn.p); hipHostFree(ctx->hLdOut.p);
+    for (int i = 0; i < 3; i++) if (ctx->ldEv[i]) (void) hipEventDestroy(ctx->ldEv[i]);
     if (ctx->swLong) (void) hipStreamDestroy(ctx->swLong);
     if (ctx->swHi) (void) hipStreamDestroy(ctx->swHi);
     hipHostFree(ctx->hPssm.p); hipHostFree(ctx->hImg.p); hipHostFree(ctx->hTids.p);
@@ -128,6 +129,7 @@ void fsgpu_sw_last_passes(const fsgpu_ctx *ctx, double *out) {
 
 double fsgpu_last_kernel_ms(const fsgpu_ctx *ctx, int which) {
     if (ctx && which >= 2 && which < 14) return ctx->kmerMs[which - 2];
+    if (ctx && (which == 14 || which == 15)) return ctx->ldMs[which - 14];
     if (!ctx || which < 0 || which > 1 || !ctx->evValid[which]) return -1.0;
     if (which == 0 && ctx->mqScanMs >= 0) return ctx->mqScanMs;      // a multi-query call with row-tiled queries: all of its scans
     float ms = 0;

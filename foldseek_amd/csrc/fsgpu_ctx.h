@@ -137,6 +137,15 @@ struct fsgpu_ctx {
     int btWgPerCU = 0;                          // fsgpu_block_backtrace_footprint: workgroups per CU of k_block_backtrace (0: default)
     DevBuf btSeq, btTrace, btBlocks, btOut, btIn;  // fsgpu_block_backtrace (k_btrace.hpp): padded reversed prefixes, trace words, block lists, [backtraces | results], inputs
     PinBuf hBtIn, hBtOut;
+    // fsgpu_lddt_batch (k_lddt.hpp): [query coordinates | target coordinates | backtraces | descriptors], per-residue norms, per-column workspace,
+    // [per-column scores | alignment lengths]; host-side planning arrays kept between calls; device ms of the last call's two kernels
+    DevBuf ldIn, ldNorm, ldCols, ldOut;
+    PinBuf hLdIn, hLdOut;
+    hipEvent_t ldEv[3] = {nullptr, nullptr, nullptr};
+    double ldMs[2] = {-1, -1};
+    std::vector<float> ldNormQuery;             // single-query calls (the one-by-one path of structurealign): the coordinates whose norms ldNorm holds, empty = none
+    std::vector<uint32_t> ldOrder, ldCounts;
+    std::vector<uint64_t> ldColOff;
     struct {
         bool pending = false;
         int n = 0, L = 0, go = 0, ge = 0;

@@ -42,7 +42,8 @@ bool DbReader::openInsideIndex(const std::string &idxPath, std::string &err, uin
     if (!outer.open(idxPath + "\x01raw", err)) return false;
     const int64_t iIdx = outer.idOf(indexKey), iDat = outer.idOf(dataKey);
     if (iIdx < 0 || iDat < 0) {
-        err = idxPath + (indexKey == 5 ? ": no sequence database inside the index (DBR1INDEX / DBR1DATA missing)" : ": no header database inside the index (HDR1INDEX / HDR1DATA missing)");
+        err = idxPath + (indexKey == 5 ? ": no sequence database inside the index (DBR1INDEX / DBR1DATA missing)" :
+                         indexKey == 500 ? ": no C-alpha database inside the index (user keys 500 / 501 missing)" : ": no header database inside the index (HDR1INDEX / HDR1DATA missing)");
         return false;
     }
     const char *p = outer.data((size_t) iIdx);
@@ -78,6 +79,23 @@ bool DbReader::openHeaders(const std::string &db, std::string &err) {
     uint64_t sz;
     if (!idx || (fileSize(plain + ".dbtype", sz) && fileSize(plain + ".index", sz))) return open(plain, err);
     return openInsideIndex(db, err, 18, 19);
+}
+
+bool DbReader::caExists(const std::string &db) {
+    uint64_t sz;
+    if (!endsWith(db, ".idx")) return fileSize(db + "_ca.dbtype", sz);
+    if (fileSize(db.substr(0, db.size() - 4) + "_ca.dbtype", sz)) return true;
+    DbReader outer;
+    std::string err;
+    return outer.open(db + "\x01raw", err) && outer.idOf(500) >= 0 && outer.idOf(501) >= 0;
+}
+
+bool DbReader::openCa(const std::string &db, std::string &err) {
+    const bool idx = endsWith(db, ".idx");
+    const std::string plain = (idx ? db.substr(0, db.size() - 4) : db) + "_ca";
+    uint64_t sz;
+    if (!idx || (fileSize(plain + ".dbtype", sz) && fileSize(plain + ".index", sz))) return open(plain, err);
+    return openInsideIndex(db, err, 500, 501);
 }
 
 bool DbReader::open(const std::string &pathIn, std::string &err) {

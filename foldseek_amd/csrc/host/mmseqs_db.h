@@ -28,6 +28,10 @@ public:
     // the header database of `db` (which may name a precomputed index): <db>_h if it exists, else the copy inside <db>.idx (entries
     // HDR1INDEX = 18 / HDR1DATA = 19, what the reference's IndexReader(..., SRC_HEADERS) reads, M/src/commons/IndexReader.h:55-75)
     bool openHeaders(const std::string &db, std::string &err);
+    // the C-alpha database of `db` (which may name a precomputed index): <db>_ca if it exists, else the copy inside <db>.idx under the user keys
+    // 500 / 501 (LocalParameters::INDEX_DB_CA_KEY_DB1, appended by createindex: F/data/structureindex.sh, M/src/util/appenddbtoindex.cpp)
+    bool openCa(const std::string &db, std::string &err);
+    static bool caExists(const std::string &db);
     size_t size() const { return entries.size(); }
     uint32_t key(size_t id) const { return entries[id].key; }
     const char *data(size_t id) const { return base + entries[id].offset; }

@@ -106,7 +106,7 @@ const FlagSpec kUngappedFlags[] = {            // Parameters::ungappedprefilter 
 
 const FlagSpec kAlignFlags[] = {               // LocalParameters::structurealign = structurealign + Parameters::align
     {"--tmscore-threshold", false, ONLY, "0|0.0|0.000"}, {"--tmscore-threshold-mode", false, IGNORE, nullptr},
-    {"--lddt-threshold", false, ONLY, "0|0.0|0.000"},
+    {"--lddt-threshold", false, USE, nullptr},  // structurealign / search: LDDT on the device (k_lddt.hpp); structurerescorediagonal refuses a non-zero value itself
     {"--alignment-type", false, ONLY, "0|2"}, {"--exact-tmscore", false, IGNORE, nullptr},
     {"-a", true, USE, "0"}, {"--add-backtrace", true, USE, "0"}, {"--alignment-mode", false, ONLY, "0|3"},
     {"--alignment-output-mode", false, ONLY, "0"}, {"--wrapped-scoring", true, ONLY, "0"}, {"-e", false, USE, nullptr},
@@ -429,6 +429,46 @@ bool resolveStructureBits(const Options &o, const std::string &qdb, const std::s
     fprintf(stderr, "Cannot find %s C-alpha or %s C-alpha database\nDisabling --sort-by-structure-bits\n", qdb.c_str(), tdb.c_str());
     return true;
 }
+
+// --lddt-threshold T > 0 (structurealign.cpp:177-250): both C-alpha databases are needed; without one of them the reference prints two warning
+// lines and carries on without the filter -- so do we.  Target entries are looked up by KEY: a padded target's _ca is keyed by the padded ids
+// (F/data/makepaddeddb.sh:39-41), like its AA database in loadPadded; through an index target the _ca lives inside <db>.idx (user keys 500 / 501).
+struct CaBinding {
+    DbReader q, tOwn;
+    const DbReader *t = nullptr;
+    std::vector<uint64_t> tOff;             // by target index, relative to t->dataBase()
+    std::vector<uint32_t> tLen;
+    float thr = 0.0f;
+    bool on = false;
+    bool open(const Options &o, const std::string &qdb, const std::string &tdb, bool sameDB, const PaddedTarget &pt, std::string &err) {
+        thr = (float) o.getd("--lddt-threshold", 0.0);
+        if (!(thr > 0.0f)) return true;
+        if (!DbReader::caExists(qdb) || !DbReader::caExists(tdb)) {
+            fprintf(stderr, "Cannot use --lddt-threshold with --sort-by-structure-bits 0\nDisabling --lddt-threshold\n");
+            return true;
+        }
+        if (!q.openCa(qdb, err)) return false;
+        if (sameDB) t = &q;
+        else { if (!tOwn.openCa(tdb, err)) return false; t = &tOwn; }
+        const size_t n = pt.keys.size();
+        tOff.resize(n); tLen.resize(n);
+        for (size_t i = 0; i < n; i++) {
+            const int64_t id = t->idOf(pt.keys[i]);
+            if (id < 0) { err = "C-alpha target database has no entry with key " + std::to_string(pt.keys[i]); return false; }
+            tOff[i] = t->offset((size_t) id); tLen[i] = t->entryLen((size_t) id);
+        }
+        on = true;
+        return true;
+    }
+    bool bind(fshost_search *s) const { return !on || fshost_search_bind_ca(s, thr, t->dataBase(), tOff.data(), tLen.data()) == FSGPU_OK; }
+    // the C-alpha entry of a query key for fshost_search_set_query_ca
+    bool queryEntry(uint32_t key, const char *&entry, uint32_t &len) const {
+        const int64_t id = q.idOf(key);
+        if (id < 0) return false;
+        entry = q.data((size_t) id); len = q.entryLen((size_t) id);
+        return true;
+    }
+};
 
 // ---- devices ------------------------------------------------------------------------------------------------------
 // --gpus N (or "all"): the target DB is loaded once on --gpu-device, replicated to N - 1 more devices with ONE broadcast
@@ -980,6 +1020,8 @@ int fsmod_search(int argc, const char **argv) {
     if (!m8 || !m2) return fail("matrix construction failed");
     PaddedTarget pt;
     if (!loadPadded(t3, &tA, m3, &mA, pt, err)) return fail(err);
+    CaBinding ca;
+    if (!ca.open(o, o.pos[0], o.pos[1], sameDB, pt, err)) return fail(err);
     const double tLoaded = nowSec();
     DeviceSet ds;
     if (!ds.open(o, pt, true, 3, err, true)) { ds.close(); return fail(err); }
@@ -1016,6 +1058,9 @@ int fsmod_search(int argc, const char **argv) {
         fsgpu_ctx *ctx = ds.forThread(tix, owned);
         if (!ctx) { bad++; return; }
         fshost_search *s = fshost_search_create(ctx, &par, pt.keys.data(), nullptr, pt.d3, pt.dA, pt.offsets.data(), pt.lengths.data());
+        if (!ca.bind(s)) { if (!bad++) firstErr = fshost_search_error(s); }
+        std::vector<const char *> caE(batch);
+        std::vector<uint32_t> caL(batch);
         std::vector<std::vector<uint8_t>> cA(batch), c3(batch);
         std::vector<std::vector<int16_t>> thr(batch);
         std::vector<std::vector<int8_t>> prof(batch);
@@ -1057,6 +1102,7 @@ int fsmod_search(int argc, const char **argv) {
                 const char *sA = qA.data((size_t) aid), *s3 = q3.data(id);
                 for (uint32_t i = 0; i < L; i++) { cA[k][i] = mA.aa2num[(unsigned char) sA[i]]; c3[k][i] = m3.aa2num[(unsigned char) s3[i]]; }
                 ident[k] = (sameDB || includeIdentical) ? t3.idOf(q3.key(id)) : -1;
+                if (ca.on && !ca.queryEntry(q3.key(id), caE[k], caL[k])) { if (!bad++) firstErr = "query key " + std::to_string(q3.key(id)) + " has no C-alpha entry"; break; }
                 Ls[k] = (int) L; pA[k] = cA[k].data(); p3[k] = c3[k].data();
                 ids[k].clear();
             }
@@ -1071,6 +1117,7 @@ int fsmod_search(int argc, const char **argv) {
                 const size_t rcap = (size_t) maxRes * (size_t) (1 + std::max(0, par.altAlignment));
                 kres.resize(batch * rcap);
                 double sec[4] = {0, 0, 0, 0};
+                if (ca.on) fshost_search_set_query_ca(s, (int) nb, caE.data(), caL.data());
                 if (fshost_search_kmer_batch(s, m8, m2, &sp, kmerThr, spaced, (int) nb, pA.data(), p3.data(), Ls.data(), ident.data(), alnIdent.data(), khits.data(), nout.data(), status.data(),
                                              kkept.data(), nkept.data(), kres.data(), knres.data(), sec) != FSGPU_OK) { if (!bad++) firstErr = fshost_search_error(s); break; }
                 usPrep += (int64_t) (sec[0] * 1e6); usPref += (int64_t) ((sec[1] + sec[2]) * 1e6); usAlign += (int64_t) (sec[3] * 1e6);
@@ -1136,6 +1183,11 @@ int fsmod_search(int argc, const char **argv) {
                 lL.push_back(Ls[k]); lN.push_back((int) ids[k].size());
                 // structurealign compares the query's and the target's INDEX in their readers (structurealign.cpp:359)
                 lI.push_back((sameDB || includeIdentical) ? (int64_t) qid[k] : -1);
+            }
+            if (ca.on) {
+                std::vector<const char *> e; std::vector<uint32_t> l;
+                for (size_t k : live) { e.push_back(caE[k]); l.push_back(caL[k]); }
+                fshost_search_set_query_ca(s, (int) live.size(), e.data(), l.data());
             }
             if (fshost_search_align_batch(s, (int) live.size(), lA.data(), l3.data(), lL.data(), lI.data(), lT.data(), lN.data(), lR.data(), lres.data()) != FSGPU_OK) {
                 if (!bad++) firstErr = fshost_search_error(s);
@@ -1204,6 +1256,8 @@ int fsmod_structurealign(int argc, const char **argv) {
     mA.builtin(FSHOST_MAT_BLOSUM62, par.alignmentType == 2 ? 1.4f : 0.0f, 0.0f);
     PaddedTarget pt;
     if (!loadPadded(t3, &tA, m3, &mA, pt, err)) return fail(err);
+    CaBinding ca;
+    if (!ca.open(o, o.pos[0], o.pos[1], sameDB, pt, err)) return fail(err);
     DeviceSet ds;
     if (!ds.open(o, pt, true, 3, err, true)) { ds.close(); return fail(err); }
     DbWriter w;
@@ -1222,6 +1276,9 @@ int fsmod_structurealign(int argc, const char **argv) {
         fsgpu_ctx *ctx = ds.forThread(tix, owned);
         if (!ctx) { bad++; return; }
         fshost_search *s = fshost_search_create(ctx, &par, pt.keys.data(), nullptr, pt.d3, pt.dA, pt.offsets.data(), pt.lengths.data());
+        if (!ca.bind(s)) { if (!bad++) firstErr = fshost_search_error(s); }
+        std::vector<const char *> caE(group);
+        std::vector<uint32_t> caL(group);
         std::vector<std::vector<uint8_t>> cA(group), c3(group);
         std::vector<std::vector<uint32_t>> ids(group);
         std::vector<std::vector<fshost_result>> res(group);
@@ -1244,6 +1301,7 @@ int fsmod_structurealign(int argc, const char **argv) {
                 if (qid < 0 || qA.idOf(queryKey) < 0) { if (!bad++) firstErr = "query key missing in query database"; break; }
                 const uint32_t L = q3.seqLen((size_t) qid);
                 if (qA.seqLen((size_t) qA.idOf(queryKey)) != L) { if (!bad++) firstErr = "query AA / 3Di entries do not match"; break; }
+                if (ca.on && !ca.queryEntry(queryKey, caE[m], caL[m])) { if (!bad++) firstErr = "query key " + std::to_string(queryKey) + " has no C-alpha entry"; break; }
                 cA[m].resize(L); c3[m].resize(L);
                 const char *sA = qA.data((size_t) qA.idOf(queryKey)), *s3 = q3.data((size_t) qid);
                 for (uint32_t i = 0; i < L; i++) { cA[m][i] = mA.aa2num[(unsigned char) sA[i]]; c3[m][i] = m3.aa2num[(unsigned char) s3[i]]; }
@@ -1268,6 +1326,7 @@ int fsmod_structurealign(int argc, const char **argv) {
             }
             if (bad) break;
             if (m == 0) continue;
+            if (ca.on) fshost_search_set_query_ca(s, (int) m, caE.data(), caL.data());
             if (fshost_search_align_batch(s, (int) m, pA.data(), p3.data(), Ls.data(), ident.data(), pT.data(), ns.data(), pR.data(), nres.data()) != FSGPU_OK) {
                 if (!bad++) firstErr = fshost_search_error(s);
                 break;
@@ -1304,6 +1363,8 @@ int fsmod_structurerescorediagonal(int argc, const char **argv) {
     }
     if (o.pos.size() != 4) return fail("usage: structurerescorediagonal <queryDB> <targetDB> <prefDB> <outAlnDB> [-e E] [-c C --cov-mode M] [--alignment-type 0|2] [-a] [--threads T] ...");
     if (o.geti("--alt-ali", 0) != 0) return fail("structurerescorediagonal: --alt-ali is not read by this module");
+    if (o.getd("--lddt-threshold", 0.0) != 0.0)
+        return fail("structurerescorediagonal: --lddt-threshold " + o.kv["--lddt-threshold"] + " is not implemented on the device path (supported: 0)");
     std::string err;
     DbReader qA, q3, tA, t3, pref;
     if (!qA.open(o.pos[0], err) || !q3.open(dbPathWithSuffix(o.pos[0], "_ss"), err) || !tA.open(o.pos[1], err) || !t3.open(dbPathWithSuffix(o.pos[1], "_ss"), err) ||
@@ -1807,14 +1868,15 @@ int fsmod_gpuserver(int argc, const char **argv) {
 // ---- convertalis -------------------------------------------------------------------------------------------------
 // F/src/strucclustutils/structureconvertalis.cpp:253-1445 for the BLAST-tab family (--format-mode 0, 2, 4) and every
 // --format-output column that is a function of the alignment record, the sequences and the headers.  Columns computed from
-// C-alpha coordinates (lddt, lddtfull, alntmscore, qtmscore, ttmscore, rmsd, u, t, qca, tca), taxonomy and multimer
-// columns are refused by name.  `prob` only reads the score (CalcProbTP.h), so it is answered without the _ca DB the reference
+// C-alpha coordinates other than LDDT (alntmscore, qtmscore, ttmscore, rmsd, u, t, qca, tca), taxonomy and multimer
+// columns are refused by name.  lddt / lddtfull (:660-680,770-773,1095-1107) are answered by the device entry fsgpu_lddt_batch: a context is
+// opened only when one of the two is asked for, and without <db>_ca they are refused like the others.  `prob` only reads the score (CalcProbTP.h), so it is answered without the _ca DB the reference
 // insists on opening for it.
 namespace {
 
 enum ConvCol { C_QUERY, C_TARGET, C_QKEY, C_TKEY, C_EVALUE, C_GAPOPEN, C_PIDENT, C_FIDENT, C_NIDENT, C_QSTART, C_QEND, C_QLEN, C_TSTART, C_TEND,
                C_TLEN, C_ALNLEN, C_BITS, C_CIGAR, C_QSEQ, C_TSEQ, C_Q3DI, C_T3DI, C_QHEADER, C_THEADER, C_QALN, C_TALN, C_Q3DIALN, C_T3DIALN,
-               C_MISMATCH, C_QCOV, C_TCOV, C_EMPTY, C_PROB, C_QSET, C_QSETID, C_TSET, C_TSETID };
+               C_MISMATCH, C_QCOV, C_TCOV, C_EMPTY, C_PROB, C_QSET, C_QSETID, C_TSET, C_TSETID, C_LDDT, C_LDDTFULL };
 
 struct ConvColSpec { const char *name; ConvCol col; bool needSeq, need3Di, needBt; int needSets = 0; };   // needSets: 1 = .lookup, 2 = .source
 const ConvColSpec kConvCols[] = {        // LocalParameters::getOutputFormat (LocalParameters.cpp:464-553)
@@ -1829,8 +1891,10 @@ const ConvColSpec kConvCols[] = {        // LocalParameters::getOutputFormat (Lo
     {"qcov", C_QCOV, false, false, false}, {"tcov", C_TCOV, false, false, false}, {"empty", C_EMPTY, false, false, false}, {"prob", C_PROB, false, false, false},
     // set columns: `tset` asks for the lookup only (LocalParameters.cpp:519), so on its own it prints the empty source name -- reproduced
     {"qset", C_QSET, false, false, false, 3}, {"qsetid", C_QSETID, false, false, false, 3}, {"tset", C_TSET, false, false, false, 1},
-    {"tsetid", C_TSETID, false, false, false, 3}};
-const char *const kConvRefused[] = {"qca", "tca", "u", "t", "alntmscore", "qtmscore", "ttmscore", "rmsd", "lddt", "lddtfull",
+    {"tsetid", C_TSETID, false, false, false, 3},
+    // backtrace columns; the query length comes from the sequence database, as in the reference (:663-664)
+    {"lddt", C_LDDT, true, false, true}, {"lddtfull", C_LDDTFULL, true, false, true}};
+const char *const kConvRefused[] = {"qca", "tca", "u", "t", "alntmscore", "qtmscore", "ttmscore", "rmsd",
                                     "taxid", "taxname", "taxlineage", "complexqtmscore", "multimerqtmscore", "complexttmscore", "multimerttmscore",
                                     "complexassignid", "multimerassignid", "complexu", "multimeru", "complext", "multimert", "qcomplexcoverage",
                                     "qmultimercoverage", "tcomplexcoverage", "tmultimercoverage", "qchaintms", "tchaintms", "qchains", "tchains", "interfacelddt"};
@@ -1946,6 +2010,106 @@ void appendAlignedSeq(std::string &out, const char *seq, unsigned int offset, co
 void appendF3(std::string &out, float x) { char b[64]; out.append(b, (size_t) snprintf(b, sizeof(b), "%.3f", (double) x)); }        // SSTR(float): fmt "{:.3f}"
 void appendE3(std::string &out, double x) { char b[64]; out.append(b, (size_t) snprintf(b, sizeof(b), "%.3E", x)); }               // SSTR(double): fmt "{:.3E}"
 
+// writeFloat3 (structureconvertalis.cpp:81-117): three decimals, half rounded up on val * 1000.0 + 0.5 -- not printf
+void appendFloat3(std::string &out, float val) {
+    if (val < 0.0f) { out.push_back('-'); val = -val; }
+    const unsigned int iv = (unsigned int) ((double) val * 1000.0 + 0.5);
+    char b[32];
+    out.append(b, (size_t) snprintf(b, sizeof(b), "%u.%03u", iv / 1000, iv % 1000));
+}
+
+// LDDT of the records of ONE chunk of alignment entries, in the order the output loop walks them: per record the average and scoreLength, and the
+// per-column values when lddtfull asks for them.  The output loop computes a chunk, prints it and drops it: memory is bounded by the chunk.
+struct ConvLddt {
+    std::vector<double> avg;
+    std::vector<int32_t> scoreLen;
+    std::vector<uint64_t> off;
+    std::vector<float> cols;
+    void clear() { avg.clear(); scoreLen.clear(); off.clear(); cols.clear(); }
+};
+struct ConvLddtRun {
+    fsgpu_ctx *ctx = nullptr;
+    ~ConvLddtRun() { if (ctx) fsgpu_destroy(ctx); }
+    bool open(int device, std::string &err) {
+        if (fsgpu_create(device, &ctx) == FSGPU_OK) return true;
+        err = std::string("GPU: ") + fsgpu_last_error(nullptr);
+        return false;
+    }
+    // entries order[oi0 .. oi1) of the alignment DB: one device call
+    bool chunk(const DbReader &aln, const std::vector<size_t> &order, size_t oi0, size_t oi1, const DbReader &qSeq, const DbReader &qCa, const DbReader &tCa,
+               bool keepCols, ConvLddt &out, std::string &err);
+    std::vector<std::vector<float>> qCoords;
+    std::vector<fsgpu_lddt_query> queries;
+    std::vector<fsgpu_lddt_task> tasks;
+    std::vector<float> tCoords, colBuf;
+    std::map<std::pair<uint32_t, int>, uint64_t> tWhere;          // (target key, length) -> offset in tCoords
+    std::string bts, bt;
+    std::vector<int32_t> lens;
+};
+bool ConvLddtRun::chunk(const DbReader &aln, const std::vector<size_t> &order, size_t oi0, size_t oi1, const DbReader &qSeq, const DbReader &qCa,
+                        const DbReader &tCa, bool keepCols, ConvLddt &out, std::string &err) {
+    out.clear();
+    qCoords.clear(); tasks.clear(); tCoords.clear(); tWhere.clear(); bts.clear();
+    uint64_t outOff = 0;
+    bool ok = true;
+    auto flush = [&]() {
+        if (tasks.empty()) return true;
+        queries.resize(qCoords.size());
+        for (size_t i = 0; i < qCoords.size(); i++) { queries[i].ca = qCoords[i].data(); queries[i].L = (int32_t) (qCoords[i].size() / 3); queries[i].reserved = 0; }
+        lens.resize(tasks.size()); colBuf.resize(std::max<uint64_t>(outOff, 1));
+        if (fsgpu_lddt_batch(ctx, queries.data(), (int) queries.size(), tasks.data(), (int) tasks.size(), tCoords.data(), tCoords.size(), bts.data(), bts.size(),
+                             lens.data(), colBuf.data(), outOff) != FSGPU_OK) { err = std::string("convertalis: ") + fsgpu_last_error(ctx); return false; }
+        for (size_t t = 0; t < tasks.size(); t++) {
+            int sl = 0;
+            out.avg.push_back(fshost_lddt_average(colBuf.data() + tasks[t].outOff, lens[t], &sl));
+            out.scoreLen.push_back(sl); out.off.push_back(out.cols.size());
+            if (keepCols) out.cols.insert(out.cols.end(), colBuf.begin() + (ptrdiff_t) tasks[t].outOff, colBuf.begin() + (ptrdiff_t) (tasks[t].outOff + (uint64_t) lens[t]));
+        }
+        return true;
+    };
+    for (size_t oi = oi0; oi < oi1 && ok; oi++) {
+        const size_t i = order[oi];
+        const uint32_t queryKey = aln.key(i);
+        const char *data = aln.data(i), *dataEnd = data + aln.entryLen(i);
+        if (data == dataEnd || *data == '\0') continue;
+        const int64_t qs = qSeq.idOf(queryKey), qc = qCa.idOf(queryKey);
+        if (qs < 0 || qc < 0) { err = "convertalis: query key " + std::to_string(queryKey) + " has no sequence or no C-alpha entry"; ok = false; break; }
+        const int Lq = (int) qSeq.seqLen((size_t) qs);
+        qCoords.emplace_back(3 * (size_t) std::max(Lq, 1));
+        if (Lq <= 0 || fshost_ca_decode(qCa.data((size_t) qc), qCa.entryLen((size_t) qc), Lq, qCoords.back().data()) != 0) {
+            err = "convertalis: the C-alpha entry of query " + std::to_string(queryKey) + " is shorter than its sequence needs"; ok = false; break;
+        }
+        while (data < dataEnd && *data != '\0') {
+            const char *lineEnd = data;
+            while (lineEnd < dataEnd && *lineEnd != '\n' && *lineEnd != '\0') lineEnd++;
+            AlnRecord res;
+            if (!parseAlnRecord(data, lineEnd, res, err)) { ok = false; break; }
+            data = (lineEnd < dataEnd && *lineEnd == '\n') ? lineEnd + 1 : lineEnd;
+            if (res.backtrace.empty()) { err = "Backtrace cigar is missing in the alignment result. Please recompute the alignment with the -a flag."; ok = false; break; }
+            if (!expandBacktrace(res.backtrace, (size_t) std::max(res.qLen, 0) + (size_t) std::max(res.dbLen, 0) + 1, bt) || res.dbLen <= 0) {
+                err = "convertalis: the alignment of query " + std::to_string(queryKey) + " with target " + std::to_string(res.dbKey) + " does not fit the databases"; ok = false; break;
+            }
+            auto it = tWhere.find({res.dbKey, res.dbLen});
+            if (it == tWhere.end()) {
+                const int64_t tc = tCa.idOf(res.dbKey);
+                const size_t at = tCoords.size();
+                tCoords.resize(at + 3 * (size_t) res.dbLen);
+                if (tc < 0 || fshost_ca_decode(tCa.data((size_t) tc), tCa.entryLen((size_t) tc), res.dbLen, tCoords.data() + at) != 0) {
+                    err = "convertalis: target key " + std::to_string(res.dbKey) + " has no C-alpha entry of " + std::to_string(res.dbLen) + " residues"; ok = false; break;
+                }
+                it = tWhere.emplace(std::make_pair(res.dbKey, res.dbLen), (uint64_t) at).first;
+            }
+            fsgpu_lddt_task t;
+            t.query = (uint32_t) (qCoords.size() - 1); t.tLen = res.dbLen; t.tOff = it->second; t.qStart = res.qStart; t.dbStart = res.dbStart;
+            t.btOff = bts.size(); t.btLen = (uint32_t) bt.size(); t.reserved = 0; t.outOff = outOff;
+            bts += bt;
+            outOff += (uint64_t) std::count(bt.begin(), bt.end(), 'M');
+            tasks.push_back(t);
+        }
+    }
+    return ok && flush();
+}
+
 float probTruePositive(float score) {          // CalcProbTP::calculate (F/src/commons/CalcProbTP.h:8-32), float arithmetic as written there
     if (score <= 10) return 0;
     if (score >= 100) return 1.0;
@@ -2003,7 +2167,12 @@ extern "C" int fsmod_convertalis(int argc, const char **argv) {
     }
     const bool sameDB = o.pos[0] == o.pos[1];
     std::string err;
-    DbReader qSeq, tSeqOwn, q3, t3Own, qHdr, tHdrOwn, aln;
+    std::string lddtCol;
+    for (size_t c = 0; c < cols.size(); c++) if ((cols[c] == C_LDDT || cols[c] == C_LDDTFULL) && lddtCol.empty()) lddtCol = colNames[c];
+    if (!lddtCol.empty() && format == 2) lddtCol.clear();          // --format-mode 2 prints its fixed columns
+    if (!lddtCol.empty() && (!DbReader::caExists(o.pos[0]) || !DbReader::caExists(o.pos[1])))
+        return fail("convertalis: column " + lddtCol + " is not implemented on this path for databases without C-alpha coordinates (no <db>_ca)");
+    DbReader qSeq, tSeqOwn, q3, t3Own, qHdr, tHdrOwn, aln, qCa, tCaOwn;
     if (!qHdr.openHeaders(o.pos[0], err)) return fail(err);
     if (!sameDB && !tHdrOwn.openHeaders(o.pos[1], err)) return fail(err);
     if (needSeq && (!qSeq.open(o.pos[0], err) || (!sameDB && !tSeqOwn.open(o.pos[1], err)))) return fail(err);
@@ -2033,6 +2202,16 @@ extern "C" int fsmod_convertalis(int argc, const char **argv) {
     for (size_t i = 0; i < order.size(); i++) order[i] = i;
     std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return aln.offset(a) < aln.offset(b); });
 
+    // lddt / lddtfull: computed chunk by chunk of alignment entries (about 256 KB of records, one device call each) right before the chunk is printed
+    ConvLddt lddt;
+    ConvLddtRun lddtRun;
+    bool wantLddtFull = false;
+    for (ConvCol c : cols) wantLddtFull = wantLddtFull || c == C_LDDTFULL;
+    if (!lddtCol.empty()) {
+        if (!qCa.openCa(o.pos[0], err) || (!sameDB && !tCaOwn.openCa(o.pos[1], err))) return fail(err);
+        if (!lddtRun.open(o.geti("--gpu-device", 0), err)) return fail(err);
+    }
+    size_t recNo = 0, chunkEnd = 0;
     FILE *plain = nullptr;
     DbWriter w;
     if (dbOut) { if (!w.open(o.pos[3], 12 /* DBTYPE_GENERIC_DB */, err)) return fail(err); }
@@ -2047,6 +2226,14 @@ extern "C" int fsmod_convertalis(int argc, const char **argv) {
     std::string result, bt;
     char buffer[1024];
     for (size_t oi = 0; oi < order.size(); oi++) {
+        if (!lddtCol.empty() && oi == chunkEnd) {
+            // the previous chunk must have used up exactly the values computed for it: the two walks see the same records
+            if (recNo != lddt.avg.size()) return fail("convertalis: internal error: " + std::to_string(recNo) + " records printed, LDDT computed for " + std::to_string(lddt.avg.size()));
+            size_t bytes = 0;
+            while (chunkEnd < order.size() && (chunkEnd == oi || bytes + aln.entryLen(order[chunkEnd]) <= ((size_t) 256 << 10))) bytes += aln.entryLen(order[chunkEnd++]);
+            if (!lddtRun.chunk(aln, order, oi, chunkEnd, qSeq, qCa, sameDB ? qCa : tCaOwn, wantLddtFull, lddt, err)) return fail(err);
+            recNo = 0;
+        }
         const size_t i = order[oi];
         const uint32_t queryKey = aln.key(i);
         const int64_t qh = qHdr.idOf(queryKey);
@@ -2065,6 +2252,7 @@ extern "C" int fsmod_convertalis(int argc, const char **argv) {
             while (lineEnd < dataEnd && *lineEnd != '\n' && *lineEnd != '\0') lineEnd++;
             AlnRecord res;
             if (!parseAlnRecord(data, lineEnd, res, err)) return fail(err);
+            const size_t rec = recNo++;
             data = (lineEnd < dataEnd && *lineEnd == '\n') ? lineEnd + 1 : lineEnd;
             if (res.backtrace.empty() && needBt)
                 return fail("Backtrace cigar is missing in the alignment result. Please recompute the alignment with the -a flag.");
@@ -2174,6 +2362,16 @@ extern "C" int fsmod_convertalis(int argc, const char **argv) {
                     case C_QSETID: result += std::to_string(qKeyToSet[queryKey]); break;
                     case C_TSET: result += tSetToSource[tKeyToSet[res.dbKey]]; break;
                     case C_TSETID: result += std::to_string(tKeyToSet[res.dbKey]); break;
+                    case C_LDDT: appendE3(result, lddt.avg[rec]); break;
+                    case C_LDDTFULL: {
+                        // the first scoreLength per-column values, NaN shown as 0 (:1099-1107).  With no scored column the reference prints the float in front
+                        // of its empty array: 0.000 in the frozen output
+                        const float *v = lddt.cols.data() + lddt.off[rec];
+                        const int sl = lddt.scoreLen[rec];
+                        for (int k = 0; k < sl; k++) { if (k) result.push_back(','); appendFloat3(result, std::isnan(v[k]) ? 0.0f : v[k]); }
+                        if (sl <= 0) appendFloat3(result, 0.0f);
+                        break;
+                    }
                 }
                 if (c + 1 < cols.size()) result.push_back('\t');
             }
@@ -2182,6 +2380,8 @@ extern "C" int fsmod_convertalis(int argc, const char **argv) {
         if (dbOut) w.write(queryKey, result.data(), result.size());
         else ioOk = ioOk && fwrite(result.data(), 1, result.size(), plain) == result.size();
     }
+    if (!lddtCol.empty() && recNo != lddt.avg.size())
+        return fail("convertalis: internal error: " + std::to_string(recNo) + " records printed, LDDT computed for " + std::to_string(lddt.avg.size()));
     if (dbOut) { if (!w.close(err)) return fail(err); }
     else {
         ioOk = (fclose(plain) == 0) && ioOk;

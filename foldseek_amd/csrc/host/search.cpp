@@ -23,6 +23,9 @@
 
 using namespace fsh;
 
+// one hit whose LDDT is wanted: query index of the call, target index, start cells, backtrace
+struct LddtJob { int q; uint32_t tid; int qStart, dbStart; const std::string *bt; };
+
 struct fshost_search {
     fsgpu_ctx *ctx = nullptr;
     fshost_params par;
@@ -48,6 +51,27 @@ struct fshost_search {
     std::vector<std::vector<int16_t>> kThr;     // fshost_search_kmer_batch: per-query k-mer thresholds / ungapped profiles of the last batch
     std::vector<std::vector<int8_t>> kProf;
     std::vector<fsgpu_kmer_query> kq;
+    // LDDT filter (fshost_search_bind_ca / fshost_search_set_query_ca): threshold, the target C-alpha entries by target index (borrowed), the query
+    // entries of the next align call, the decoded query coordinates of the running one, staging of a fsgpu_lddt_batch call
+    float lddtThr = 0.0f;
+    const char *tCaBase = nullptr;
+    const uint64_t *tCaOff = nullptr;
+    const uint32_t *tCaLen = nullptr;
+    std::vector<const char *> qCaEntry;
+    std::vector<uint32_t> qCaLen;
+    std::vector<std::vector<float>> qCa;
+    std::vector<float> ldT, ldOut;
+    std::string ldBt;
+    std::vector<fsgpu_lddt_task> ldTasks;
+    std::vector<fsgpu_lddt_query> ldQ;
+    std::vector<int32_t> ldLen;
+    std::vector<uint32_t> ldTids, ldQLen;       // host-side planning of the LDDT calls, kept between them like the staging above
+    std::vector<uint64_t> ldTOff;
+    std::vector<const char *> ldQEntry;
+    std::vector<size_t> ldWhere;
+    std::vector<double> ldAvg;
+    std::vector<LddtJob> ldJobs;
+    bool lddtOn() const { return lddtThr > 0.0f && tCaBase != nullptr; }
     // host-side wall time of the last calls, seconds: [0] prefilter profile, [1] prefilter device call (incl. wait),
     // [2] align profiles + e-value net, [3] SW device call (incl. wait), [4] gates, [5] block-aligner backtrace
     double stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -197,6 +221,20 @@ fshost_search *fshost_search_create(fsgpu_ctx *ctx, const fshost_params *p, cons
 }
 
 void fshost_search_free(fshost_search *s) { delete s; }
+
+int fshost_search_bind_ca(fshost_search *s, float lddtThr, const char *caBase, const uint64_t *caOffsets, const uint32_t *caLengths) {
+    if (!s) return FSGPU_E_ARG;
+    if (!(lddtThr > 0.0f) || !caBase) { s->lddtThr = 0.0f; s->tCaBase = nullptr; s->tCaOff = nullptr; s->tCaLen = nullptr; return FSGPU_OK; }
+    if (!caOffsets || !caLengths) { s->err = "fshost_search_bind_ca: offsets and lengths are required"; return FSGPU_E_ARG; }
+    s->lddtThr = lddtThr; s->tCaBase = caBase; s->tCaOff = caOffsets; s->tCaLen = caLengths;
+    return FSGPU_OK;
+}
+int fshost_search_set_query_ca(fshost_search *s, int nq, const char *const *entries, const uint32_t *lengths) {
+    if (!s || nq < 0 || (nq > 0 && (!entries || !lengths))) return FSGPU_E_ARG;
+    s->qCaEntry.assign(entries, entries + nq);
+    s->qCaLen.assign(lengths, lengths + nq);
+    return FSGPU_OK;
+}
 const char *fshost_search_error(const fshost_search *s) { return s ? s->err.c_str() : "null handle"; }
 
 int fshost_search_prefilter(fshost_search *s, const uint8_t *q3di, int L, int64_t identityId, fsgpu_hit *hits) {
@@ -282,6 +320,7 @@ struct AlignQuery {
     std::vector<int16_t> pAAf, p3f, pAAr, p3r;
     std::vector<int8_t> cbAA, cbSS, cbAAr, cbSSr;       // r: biases of the reversed query, indexed by reversed position
     double lambda = 0, mu = 0;
+    const float *ca = nullptr;                          // x[L] y[L] z[L] when the LDDT filter is on
 };
 
 // the four word profiles from codes + biases (StructureSmithWaterman.cpp:1566-1640: matrix column + position bias)
@@ -443,13 +482,105 @@ int alternativeAlignments(fshost_search *s, const AlignQuery &aq, uint32_t tid, 
     return FSGPU_OK;
 }
 
+// The result record of a pair that passed the score gates (structurealign.cpp:76-112) and Alignment::checkCriteria (Alignment.cpp:548) on it; the caller sets
+// backtraceOff.  Shared by gateAlign and by the LDDT precomputation, which scores exactly the hits gateAlign will ask about.
+bool fillResult(const fshost_search *s, const AlignQuery &aq, uint32_t tid, const fsgpu_swres &f, int32_t score, double evalue, const BlockAlnOut &bo,
+                bool isIdentity, fshost_result &r) {
+    const fshost_params &par = s->par;
+    const int L = aq.L, Lt = s->lengths[tid];
+    memset(&r, 0, sizeof(r));
+    int qStart = -1, dbStart = -1;
+    float seqId = 0.0f;
+    float qCov = computeCov(0, f.qEnd, L), tCov = computeCov(0, f.dbEnd, Lt);
+    if (bo.ok) {
+        qStart = bo.qStart; dbStart = bo.dbStart;
+        qCov = computeCov(qStart, f.qEnd, L);
+        tCov = computeCov(dbStart, f.dbEnd, Lt);
+    }
+    unsigned int alnLength = std::max(abs(f.qEnd - qStart), abs(f.dbEnd - dbStart)) + 1;   // Matcher::computeAlnLength
+    if (bo.backtrace.size() > 0) {
+        alnLength = bo.backtrace.size();
+        // Util::computeSeqId (M/src/commons/Util.cpp:597-607)
+        const int den = par.seqIdMode == 1 ? std::min(L, Lt) : par.seqIdMode == 2 ? std::max(L, Lt) : (int) alnLength;
+        seqId = static_cast<float>(bo.identicalAA) / static_cast<float>(den);
+    }
+    r.dbKey = s->keys[tid]; r.score = score; r.qcov = qCov; r.dbcov = tCov; r.seqId = seqId; r.eval = evalue;
+    r.alnLength = alnLength; r.qStartPos = qStart; r.qEndPos = f.qEnd; r.qLen = L; r.dbStartPos = dbStart; r.dbEndPos = f.dbEnd;
+    r.dbLen = Lt; r.backtraceLen = (uint32_t) bo.backtrace.size();
+    const bool evalOk = (r.eval <= par.evalThr);
+    const bool seqIdOK = (r.seqId >= par.seqIdThr);
+    const bool covOK = hasCoverage(par.covThr, par.covMode, r.qcov, r.dbcov);
+    const bool alnLenOK = (int) r.alnLength >= par.alnLenThr;
+    return isIdentity || (evalOk && seqIdOK && covOK && alnLenOK);
+}
+
+// ---- LDDT of hits (structurealign.cpp:398-408): one fsgpu_lddt_batch call for a list of (query, target, start cells, backtrace) ----
+// decodes the query C-alpha entries handed over for this call into s->qCa and points aq[i].ca at them
+int lddtPrepareQueries(fshost_search *s, AlignQuery *aq, int nq) {
+    std::vector<const char *> &entries = s->ldQEntry;
+    std::vector<uint32_t> &lens = s->ldQLen;
+    entries.swap(s->qCaEntry); lens.swap(s->qCaLen);          // consumed by this call
+    s->qCaEntry.clear(); s->qCaLen.clear();
+    if (!s->lddtOn()) return FSGPU_OK;
+    if ((int) entries.size() != nq) { s->err = "the LDDT filter is bound but the query C-alpha entries of this call were not set (fshost_search_set_query_ca)"; return FSGPU_E_ARG; }
+    if ((int) s->qCa.size() < nq) s->qCa.resize(nq);
+    std::atomic<int> bad{-1};
+    HostPool::get().parallelFor(nq, [&](int i) {
+        s->qCa[i].resize(3 * (size_t) aq[i].L);
+        if (!entries[i] || fshost_ca_decode(entries[i], lens[i], aq[i].L, s->qCa[i].data()) != 0) bad.store(i);
+        aq[i].ca = s->qCa[i].data();
+    });
+    if (bad.load() >= 0) { s->err = "query C-alpha entry " + std::to_string(bad.load()) + " of the batch is shorter than its sequence needs"; return FSGPU_E_ARG; }
+    return FSGPU_OK;
+}
+// avg[j] = LDDTScoreResult::avgLddtScore of job j: target entries decoded on the host pool (once per distinct target), all-pairs part on the device,
+// ordered average on the host
+int lddtJobs(fshost_search *s, const AlignQuery *aq, int nq, const std::vector<LddtJob> &jobs, std::vector<double> &avg) {
+    avg.assign(jobs.size(), 0.0);
+    if (jobs.empty()) return FSGPU_OK;
+    std::vector<uint32_t> &tids = s->ldTids;
+    tids.resize(jobs.size());
+    for (size_t j = 0; j < jobs.size(); j++) tids[j] = jobs[j].tid;
+    std::sort(tids.begin(), tids.end());
+    tids.erase(std::unique(tids.begin(), tids.end()), tids.end());
+    std::vector<uint64_t> &tOff = s->ldTOff;
+    tOff.assign(tids.size() + 1, 0);
+    for (size_t u = 0; u < tids.size(); u++) tOff[u + 1] = tOff[u] + 3 * (uint64_t) s->lengths[tids[u]];
+    s->ldT.resize(tOff.back());
+    std::atomic<int64_t> bad{-1};
+    HostPool::get().parallelFor((int) tids.size(), [&](int u) {
+        const uint32_t tid = tids[u];
+        if (fshost_ca_decode(s->tCaBase + s->tCaOff[tid], s->tCaLen[tid], s->lengths[tid], s->ldT.data() + tOff[u]) != 0) bad.store((int64_t) tid);
+    });
+    if (bad.load() >= 0) { s->err = "target C-alpha entry of key " + std::to_string(s->keys[(size_t) bad.load()]) + " is shorter than its sequence needs"; return FSGPU_E_ARG; }
+    s->ldQ.resize(nq);
+    for (int i = 0; i < nq; i++) { s->ldQ[i].ca = aq[i].ca; s->ldQ[i].L = aq[i].L; s->ldQ[i].reserved = 0; }
+    s->ldTasks.resize(jobs.size()); s->ldLen.resize(jobs.size());
+    s->ldBt.clear();
+    uint64_t outOff = 0;
+    for (size_t j = 0; j < jobs.size(); j++) {
+        const LddtJob &job = jobs[j];
+        fsgpu_lddt_task &t = s->ldTasks[j];
+        const size_t u = (size_t) (std::lower_bound(tids.begin(), tids.end(), job.tid) - tids.begin());
+        t.query = (uint32_t) job.q; t.tLen = s->lengths[job.tid]; t.tOff = tOff[u]; t.qStart = job.qStart; t.dbStart = job.dbStart;
+        t.btOff = s->ldBt.size(); t.btLen = (uint32_t) job.bt->size(); t.reserved = 0; t.outOff = outOff;
+        s->ldBt.append(*job.bt);
+        outOff += (uint64_t) std::count(job.bt->begin(), job.bt->end(), 'M');
+    }
+    s->ldOut.resize(std::max<uint64_t>(outOff, 1));
+    const int rc = fsgpu_lddt_batch(s->ctx, s->ldQ.data(), nq, s->ldTasks.data(), (int) jobs.size(), s->ldT.data(), s->ldT.size(), s->ldBt.data(), s->ldBt.size(),
+                                    s->ldLen.data(), s->ldOut.data(), outOff);
+    if (rc != FSGPU_OK) { s->err = fsgpu_last_error(s->ctx); return rc; }
+    for (size_t j = 0; j < jobs.size(); j++) avg[j] = fshost_lddt_average(s->ldOut.data() + s->ldTasks[j].outOff, s->ldLen[j], nullptr);
+    return FSGPU_OK;
+}
+
 // alignStructure gates + backtrace + checkCriteria + ordering for one query (structurealign.cpp:37-112,350-445).
 // pre / preIdx: backtraces computed ahead by the worker pool (preIdx[k] = index into pre, -1 = none); without them the
 // backtrace of a pair is computed here, when the loop reaches it (the --max-accept / --max-rejected path).
 int gateAlign(fshost_search *s, const AlignQuery &aq, int64_t identityId, const uint32_t *targetIds, int n, const fsgpu_swres *fwd,
-              const fsgpu_swres *rev, fshost_result *results, double &tBack, const BlockAlnOut *pre, const int *preIdx) {
+              const fsgpu_swres *rev, fshost_result *results, double &tBack, const BlockAlnOut *pre, const int *preIdx, const double *preLddt = nullptr) {
     const fshost_params &par = s->par;
-    const int L = aq.L;
     const int resCap = n * (1 + std::max(0, par.altAlignment));
     int passedNum = 0, rejected = 0, nres = 0;
     BlockAlnOut local;
@@ -457,7 +588,6 @@ int gateAlign(fshost_search *s, const AlignQuery &aq, int64_t identityId, const 
         const uint32_t tid = targetIds[k];
         const bool isIdentity = ((int64_t) tid == identityId);
         if (tid >= s->keys.size()) { s->err = "target id out of range"; return FSGPU_E_ARG; }
-        const int Lt = s->lengths[tid];
         // ---- alignStructure ----
         const fsgpu_swres &f = fwd[k];
         int32_t score = 0;
@@ -478,31 +608,23 @@ int gateAlign(fshost_search *s, const AlignQuery &aq, int64_t identityId, const 
         }
         const BlockAlnOut &bo = *bop;
         fshost_result r;
-        memset(&r, 0, sizeof(r));
-        int qStart = -1, dbStart = -1;
-        float seqId = 0.0f;
-        float qCov = computeCov(0, f.qEnd, L), tCov = computeCov(0, f.dbEnd, Lt);
-        if (bo.ok) {
-            qStart = bo.qStart; dbStart = bo.dbStart;
-            qCov = computeCov(qStart, f.qEnd, L);
-            tCov = computeCov(dbStart, f.dbEnd, Lt);
-        }
-        unsigned int alnLength = std::max(abs(f.qEnd - qStart), abs(f.dbEnd - dbStart)) + 1;   // Matcher::computeAlnLength
-        if (bo.backtrace.size() > 0) {
-            alnLength = bo.backtrace.size();
-            // Util::computeSeqId (M/src/commons/Util.cpp:597-607)
-            const int den = par.seqIdMode == 1 ? std::min(L, Lt) : par.seqIdMode == 2 ? std::max(L, Lt) : (int) alnLength;
-            seqId = static_cast<float>(bo.identicalAA) / static_cast<float>(den);
-        }
-        r.dbKey = s->keys[tid]; r.score = score; r.qcov = qCov; r.dbcov = tCov; r.seqId = seqId; r.eval = evalue;
-        r.alnLength = alnLength; r.qStartPos = qStart; r.qEndPos = f.qEnd; r.qLen = L; r.dbStartPos = dbStart; r.dbEndPos = f.dbEnd;
-        r.dbLen = Lt; r.backtraceOff = (uint32_t) s->cigars.size(); r.backtraceLen = (uint32_t) bo.backtrace.size();
-        // Alignment::checkCriteria (Alignment.cpp:548)
-        const bool evalOk = (r.eval <= par.evalThr);
-        const bool seqIdOK = (r.seqId >= par.seqIdThr);
-        const bool covOK = hasCoverage(par.covThr, par.covMode, r.qcov, r.dbcov);
-        const bool alnLenOK = (int) r.alnLength >= par.alnLenThr;
-        if (isIdentity || (evalOk && seqIdOK && covOK && alnLenOK)) {
+        const bool accepted = fillResult(s, aq, tid, f, score, evalue, bo, isIdentity, r);
+        r.backtraceOff = (uint32_t) s->cigars.size();
+        if (accepted) {
+            if (s->lddtOn()) {
+                // structurealign.cpp:398-408: the hit is dropped by a bare `continue` -- it counts neither as accepted nor as rejected
+                double avg;
+                if (preLddt && pre && preIdx && preIdx[k] >= 0) avg = preLddt[preIdx[k]];
+                else if (!bo.ok || bo.backtrace.empty()) avg = fshost_lddt_average(nullptr, 0, nullptr);      // no aligned column: the reference's 0 / 0
+                else {
+                    s->ldJobs.assign(1, LddtJob{0, tid, bo.qStart, bo.dbStart, &bo.backtrace});
+                    const int rc = lddtJobs(s, &aq, 1, s->ldJobs, s->ldAvg);
+                    if (rc != FSGPU_OK) return rc;
+                    avg = s->ldAvg[0];
+                }
+                if (avg < (double) s->lddtThr) continue;
+                r.dbcov = (float) avg;
+            }
             s->cigars.append(bo.backtrace);
             s->cigars.push_back('\0');
             results[nres++] = r;
@@ -697,6 +819,38 @@ void precomputeBacktraces(const fshost_search *s, const std::vector<AlignQuery> 
     pb.seconds = nowSec() - t0;
 }
 
+// LDDT of the precomputed backtraces of the batch in one device call, for exactly the hits gateAlign will ask about: those that pass checkCriteria
+// (the reference computes LDDT only after it, structurealign.cpp:376-398).  lddt[index into pb.outs]; a hit without backtrace keeps the 0 / 0 the
+// reference computes for it.
+int lddtPrecomputed(fshost_search *s, const AlignQuery *aq, int nq, const int64_t *identityId, const uint32_t *const *targetIds, const int *n,
+                    const fsgpu_swres *fwd, const fsgpu_swres *rev, const PreBacktrace &pb, std::vector<double> &lddt) {
+    lddt.clear();
+    if (!s->lddtOn() || pb.outs.empty()) return FSGPU_OK;
+    std::vector<LddtJob> &jobs = s->ldJobs;
+    std::vector<size_t> &where = s->ldWhere;
+    jobs.clear(); where.clear();
+    size_t base = 0;
+    for (int i = 0; i < nq; i++) {
+        for (size_t k = 0; k < pb.idx[i].size(); k++) {
+            const int o = pb.idx[i][k];
+            if (o < 0 || !pb.outs[o].ok || pb.outs[o].backtrace.empty()) continue;
+            const uint32_t tid = targetIds[i][k];
+            int32_t score; double evalue;
+            fshost_result r;
+            if (!passesScoreGates(s, aq[i], tid, fwd[base + k], rev[base + k], score, evalue, nullptr)) continue;
+            if (!fillResult(s, aq[i], tid, fwd[base + k], score, evalue, pb.outs[o], identityId && (int64_t) tid == identityId[i], r)) continue;
+            jobs.push_back(LddtJob{i, tid, pb.outs[o].qStart, pb.outs[o].dbStart, &pb.outs[o].backtrace});
+            where.push_back((size_t) o);
+        }
+        base += (size_t) n[i];
+    }
+    const int rc = lddtJobs(s, aq, nq, jobs, s->ldAvg);
+    if (rc != FSGPU_OK) return rc;
+    lddt.assign(pb.outs.size(), fshost_lddt_average(nullptr, 0, nullptr));
+    for (size_t j = 0; j < jobs.size(); j++) lddt[where[j]] = s->ldAvg[j];
+    return FSGPU_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -710,6 +864,7 @@ int fshost_search_align(fshost_search *s, const uint8_t *qAA, const uint8_t *q3d
     AlignQuery aq;
     aq.qAA = qAA; aq.q3di = q3di; aq.L = L;
     int rc = prepareAlign(s, aq, s->rAA, s->r3Di);
+    if (rc == FSGPU_OK) rc = lddtPrepareQueries(s, &aq, 1);
     if (rc != FSGPU_OK) return rc;
     s->fwd.resize(n); s->rev.resize(n);
     const double t1 = nowSec();
@@ -727,7 +882,10 @@ int fshost_search_align(fshost_search *s, const uint8_t *qAA, const uint8_t *q3d
         aq = std::move(one[0]);
     }
     tBack += pb.seconds;
-    const int nres = gateAlign(s, aq, identityId, targetIds, n, s->fwd.data(), s->rev.data(), results, tBack, pb.outs.data(), pb.idx[0].empty() ? nullptr : pb.idx[0].data());
+    std::vector<double> preLddt;
+    if ((rc = lddtPrecomputed(s, &aq, 1, &identityId, &targetIds, &n, s->fwd.data(), s->rev.data(), pb, preLddt)) != FSGPU_OK) return rc;
+    const int nres = gateAlign(s, aq, identityId, targetIds, n, s->fwd.data(), s->rev.data(), results, tBack, pb.outs.data(), pb.idx[0].empty() ? nullptr : pb.idx[0].data(),
+                               preLddt.empty() ? nullptr : preLddt.data());
     s->stats[2] = t1 - t0; s->stats[3] = t2 - t1; s->stats[5] = tBack; s->stats[4] = nowSec() - t2 - tBack;
     return nres;
 }
@@ -762,6 +920,7 @@ int fshost_search_align_batch(fshost_search *s, int nq, const uint8_t *const *qA
         });
         if (firstErr.load() != FSGPU_OK) return firstErr.load();
     }
+    { const int rcCa = lddtPrepareQueries(s, aq.data(), nq); if (rcCa != FSGPU_OK) return rcCa; }
     for (int i = 0; i < nq; i++) {
         dq[i].qAA = qAA[i]; dq[i].q3Di = q3di[i];
         dq[i].cbAA_fwd = aq[i].cbAA.data(); dq[i].cb3Di_fwd = aq[i].cbSS.data(); dq[i].cbAA_rev = aq[i].cbAAr.data(); dq[i].cb3Di_rev = aq[i].cbSSr.data();
@@ -820,10 +979,12 @@ int fshost_search_align_batch(fshost_search *s, int nq, const uint8_t *const *qA
     PreBacktrace pb;
     precomputeBacktraces(s, aq, targetIds, n, s->fwd.data(), s->rev.data(), pb);
     tBack += pb.seconds;
+    std::vector<double> preLddt;
+    if ((rc = lddtPrecomputed(s, aq.data(), nq, identityId, targetIds, n, s->fwd.data(), s->rev.data(), pb, preLddt)) != FSGPU_OK) return rc;
     size_t base = 0;
     for (int i = 0; i < nq; i++) {
         nres[i] = gateAlign(s, aq[i], identityId ? identityId[i] : -1, targetIds[i], n[i], s->fwd.data() + base, s->rev.data() + base, results[i], tBack,
-                            pb.outs.data(), pb.idx[i].empty() ? nullptr : pb.idx[i].data());
+                            pb.outs.data(), pb.idx[i].empty() ? nullptr : pb.idx[i].data(), preLddt.empty() ? nullptr : preLddt.data());
         if (nres[i] < 0) return nres[i];
         base += (size_t) n[i];
     }
@@ -899,10 +1060,16 @@ int fshost_search_kmer_batch(fshost_search *s, const fshost_matrix *mKmer, const
     t0 = t1;
     if (!lq.empty()) {
         lres.assign(lq.size(), 0);
+        if (s->lddtOn() && (int) s->qCaEntry.size() == nq) {          // the C-alpha entries of the queries that reach the aligner, in its order
+            std::vector<const char *> e(lq.size()); std::vector<uint32_t> l(lq.size());
+            for (size_t j = 0; j < lq.size(); j++) { e[j] = s->qCaEntry[lq[j]]; l[j] = s->qCaLen[lq[j]]; }
+            s->qCaEntry.swap(e); s->qCaLen.swap(l);
+        }
         const int rc = fshost_search_align_batch(s, (int) lq.size(), lA.data(), l3.data(), lL.data(), lI.data(), lT.data(), lN.data(), lR.data(), lres.data());
         if (rc != FSGPU_OK) return rc;
         for (size_t j = 0; j < lq.size(); j++) nres[lq[j]] = lres[j];
     }
+    s->qCaEntry.clear(); s->qCaLen.clear();
     if (seconds) seconds[3] = nowSec() - t0;
     return FSGPU_OK;
 }

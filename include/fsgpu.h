@@ -26,6 +26,8 @@
  *   fsgpu_sw_multi / _multi_dir       the same for a batch of queries, one device launch per register class and direction
  *                                     (forward over all pairs, reversed over the pairs alignStructure still needs:
  *                                     F/src/strucclustutils/structurealign.cpp:50-65)
+ *   fsgpu_lddt_batch                  LDDTCalculator::initQuery / computeLDDTScore                      F/src/commons/LDDT.cpp:87-215, call sites
+ *                                     F/src/strucclustutils/structurealign.cpp:331-341,398-408, structureconvertalis.cpp:770-773
  *   fsgpu_db_broadcast                replication of the resident DB over the GPUs of a node (RCCL), SURVEY 8e
  *   fshost_*                          host-side pieces of the same path that stay on the CPU, exported so the
  *                                     reference-side adapter and the tests can reach them.
@@ -270,6 +272,29 @@ int fsgpu_block_backtrace_footprint(fsgpu_ctx *ctx, int workgroupsPerCU);
  * use by it when it decides who computes the backtraces (FSGPU_CORES_PER_GPU overrides the quotient: one rank of a multi-process job sets it to its share). */
 int fsgpu_live_devices(void);
 
+/* ---- LDDT of accepted hits: LDDTCalculator::initQuery + computeLDDTScore (F/src/commons/LDDT.{h,cpp}) for a batch of hits ----------------------------
+ * Per aligned column ('M' of the backtrace, from (qStart, dbStart)) the reference's per-residue score reduce_score[column], bit for bit: the count of
+ * preserved-distance quarters over all other aligned columns whose query distance is below 15 A, times 1 / (neighbours of the query residue among ALL
+ * query residues); NaN (0 * inf) for a query residue without neighbours.  The ordered float sum of the non-NaN columns, scoreLength and the division
+ * (LDDTScoreResult, LDDT.h:102-119) are the caller's: fshost_lddt_average.
+ * ca of a query: x[L] y[L] z[L], what Coordinate16::read hands out (fshost_ca_decode).  tCoords: the same layout per target, task k's at tOff (floats) with
+ * tLen residues; several tasks may share one.  bt: 'M' / 'I' / 'D' characters (anything else is skipped, as in the reference), task k's at btOff, btLen of them.
+ * alignLength[k] receives the number of aligned columns, out[outOff .. outOff + alignLength[k]) the per-column values (outOff + alignLength <= outCap is checked).
+ * Alignments of any length up to FSGPU_MAX_SEQ_LEN run on the device; there is no host path. */
+typedef struct { const float *ca; int32_t L; int32_t reserved; } fsgpu_lddt_query;
+typedef struct {
+    uint32_t query;         /* index into queries */
+    int32_t tLen;           /* residues of the target */
+    uint64_t tOff;          /* float offset of its coordinates in tCoords */
+    int32_t qStart, dbStart;
+    uint64_t btOff;
+    uint32_t btLen;
+    uint32_t reserved;
+    uint64_t outOff;        /* float offset of its per-column values in out */
+} fsgpu_lddt_task;
+int fsgpu_lddt_batch(fsgpu_ctx *ctx, const fsgpu_lddt_query *queries, int nq, const fsgpu_lddt_task *tasks, int nt, const float *tCoords, uint64_t tCoordsLen,
+                     const char *bt, uint64_t btBytes, int32_t *alignLength, float *out, uint64_t outCap);
+
 /* ---- prefilter: k-mer matching with double-diagonal hits + ungapped diagonal scoring ------------------------- */
 /* Index parameters == the subset of Prefiltering's members that shape IndexTable / SequenceLookup.  Sequence-
  * sequence searches with k = 6 only (what setupSplit picks below 3.35e9 residues, IndexTable.h:456-458). */
@@ -366,7 +391,8 @@ int fsgpu_kmer_plan_coarse(const int32_t *lengths, uint64_t n, uint32_t blocksPe
 /* Device time (ms, HIP events on the context stream) of the dominant kernel of the last _finish()ed call:
  * which = 0 gapless scan kernel, 1 SW kernel, 2 whole device part of the last fsgpu_kmer_search batch,
  * 3..10 its stages (similar-k-mer count, index probes, hit gather, partition into (query, bin) segments, double-diagonal
- * detection per segment, scoring, replay, selection), 11 host tail, 12 the index-probe kernel (k_kmer_lists) alone.
+ * detection per segment, scoring, replay, selection), 11 host tail, 12 the index-probe kernel (k_kmer_lists) alone,
+ * 14 / 15 the two kernels of the last fsgpu_lddt_batch (k_lddt_norm, k_lddt_pairs).
  * Returns < 0 if nothing was recorded. */
 double fsgpu_last_kernel_ms(const fsgpu_ctx *ctx, int which);
 /* out[2][4], per direction (0 forward, 1 reversed query) of the last fsgpu_sw_multi_dir calls of this context: device ms of that pass's

@@ -209,6 +209,23 @@ int fshost_banded_backtrace(const fshost_matrix *mAA, const fshost_matrix *m3Di,
                             const int8_t *cbSS, const uint8_t *tAA, const uint8_t *t3Di, int qStart, int qEnd, int dbStart, int dbEnd, int score,
                             int gapOpen, int gapExtend, unsigned int *identicalAA, char *backtrace, size_t btCap);
 
+/* ---- C-alpha coordinates and LDDT (F/src/commons/Coordinate16.h, LDDT.{h,cpp}) ----
+ * fshost_ca_decode == Coordinate16::read: a <db>_ca entry of entryLen bytes for a chain of L residues -> out = x[L] y[L] z[L].  An entry of at least
+ * 3 * L * 4 bytes is raw float32; otherwise every axis is an int32 start followed by L - 1 int16 differences, value = (start + running sum) / 1000.0f.
+ * Returns 0, or -1 when the entry is too short for the compressed form (the reference reads past it). */
+int fshost_ca_decode(const char *entry, size_t entryLen, int L, float *out);
+/* LDDTScoreResult (LDDT.h:102-119) over the per-column values fsgpu_lddt_batch returns: NaN columns are skipped and reduce *scoreLength, the float sum runs
+ * in column order, the result is (double) (sum / (float) scoreLength) -- 0 / 0 with the sign the x86 reference produces when every column is NaN. */
+double fshost_lddt_average(const float *cols, int alignLength, int *scoreLength);
+/* Binds C-alpha data and --lddt-threshold to a search handle (structurealign.cpp:177-250,331-341,376-411): with lddtThr > 0 every hit that passes
+ * Alignment::checkCriteria has its LDDT computed on the device (one fsgpu_lddt_batch per align batch) and is dropped -- neither accepted nor rejected --
+ * when the average is below the threshold; alternative alignments (--alt-ali) are not filtered.  Target entry i (target INDEX, as for `keys`) is
+ * caBase + caOffsets[i], caLengths[i] bytes as stored in <db>_ca; the three arrays are borrowed and must outlive the handle.  lddtThr <= 0 or
+ * caBase == NULL unbinds.  Query entries go with the batch: fshost_search_set_query_ca before fshost_search_align / _align_batch / _kmer_batch, entries[q]
+ * / lengths[q] for the queries of that call in their order (borrowed until it returns; consumed by it).  A bound handle refuses an align call without them. */
+int fshost_search_bind_ca(fshost_search *s, float lddtThr, const char *caBase, const uint64_t *caOffsets, const uint32_t *caLengths);
+int fshost_search_set_query_ca(fshost_search *s, int nq, const char *const *entries, const uint32_t *lengths);
+
 /* text formats: QueryMatcher::prefilterHitToBuffer (QueryMatcher.h:120-132), Matcher::resultToBuffer (Matcher.cpp:282) */
 size_t fshost_format_prefilter_hit(char *buf, uint32_t key, int score, int diagonal);
 size_t fshost_format_result(char *buf, const fshost_result *r, const char *backtrace, int addBacktrace);
