@@ -43,6 +43,11 @@ class KmerQuery(C.Structure):
 
 
 KMER_HIT_DT = np.dtype([("id", np.uint32), ("score", np.int32), ("diag", np.uint16), ("pad", np.uint16)])
+SW_DT = SWRES_DT      # fsgpu_swres under the name the oracle bindings use
+DIAG_PAIR_DT = np.dtype([("query", np.uint32), ("target", np.uint32), ("diagonal", np.int32)])      # fsgpu_diag_pair
+DIAG_RES_DT = np.dtype([("score", np.int32), ("startPos", np.int32), ("endPos", np.int32), ("revScore", np.int32), ("diagonalLen", np.int32),
+                        ("identicalAA", np.int32), ("status", np.int32), ("reserved", np.int32)])   # fsgpu_diag_res
+FSGPU_DIAG_OK, FSGPU_DIAG_NO_OVERLAP, FSGPU_DIAG_UNDEFINED, FSGPU_DIAG_BAD_ID = 0, 1, 2, 3
 
 
 class BtQuery(C.Structure):
@@ -195,7 +200,8 @@ def exported_symbols():
             "fsgpu_gapless_launch", "fsgpu_gapless_finish", "fsgpu_sw_batch", "fsgpu_sw_multi", "fsgpu_sw_multi_dir", "fsgpu_sw_multi_dir_c", "fsgpu_sw_multi_c", "fsgpu_sw_launch", "fsgpu_sw_finish",
             "fsgpu_db_broadcast", "fsgpu_rccl_selfcheck", "fsgpu_device_count", "fsgpu_live_devices", "fsgpu_gapless_plan_items", "fsgpu_block_backtrace", "fsgpu_block_backtrace_footprint",
             "fsgpu_lddt_batch", "fsgpu_last_kernel_ms", "fsgpu_sw_last_passes", "fsgpu_kmer_index_build", "fsgpu_kmer_index_entries", "fsgpu_kmer_search",
-            "fsgpu_kmer_index_copy", "fsgpu_kmer_row_copy", "fsgpu_kmer_last_counts", "fsgpu_kmer_last_segments", "fsgpu_kmer_plan_coarse", "fsgpu_kmer_batch_hint"]
+            "fsgpu_kmer_index_copy", "fsgpu_kmer_row_copy", "fsgpu_kmer_last_counts", "fsgpu_kmer_last_segments", "fsgpu_kmer_plan_coarse", "fsgpu_kmer_batch_hint",
+            "fsgpu_diag_rescore", "fsgpu_sw_batch_seqs"]
 
 
 def _ptr(a):
@@ -564,6 +570,64 @@ class Context:
         self._chk(lib().fsgpu_sw_batch(self.h, _ptr(pAAf), _ptr(p3f), _ptr(pAAr), _ptr(p3r), p3f.shape[1], _ptr(t), len(t),
                                        gap_open, gap_extend, _ptr(fwd), _ptr(rev)), "fsgpu_sw_batch")
         return fwd, rev
+
+    @staticmethod
+    def _pack_seqs(seq_lists, offsets, lengths):
+        """code arrays -> one uint8 buffer each, UNPADDED and back to back, + (offsets uint64[n + 1], lengths int32[n]); offsets / lengths given by the
+        caller are handed on as they are (the layout checks of the entries are reached that way)"""
+        n = len(seq_lists[0])
+        ln = np.array([len(s) for s in seq_lists[0]], np.int64)
+        bufs = []
+        for seqs in seq_lists:
+            if seqs is None:
+                bufs.append(None)
+                continue
+            if len(seqs) != n or any(len(s) != l for s, l in zip(seqs, ln)):
+                raise FsgpuError("the AA and 3Di sequences differ in number or length")
+            parts = [np.ascontiguousarray(s, np.uint8).reshape(-1) for s in seqs]
+            bufs.append(np.ascontiguousarray(np.concatenate(parts + [np.zeros(1, np.uint8)])))     # never an empty buffer (NULL would read as "missing")
+        off = np.concatenate([[0], np.cumsum(ln)]).astype(np.uint64) if offsets is None else np.ascontiguousarray(offsets, np.uint64)
+        lens = ln.astype(np.int32) if lengths is None else np.ascontiguousarray(lengths, np.int32)
+        if len(off) != len(lens) + 1:
+            raise FsgpuError("offsets must have one entry more than lengths")
+        if int(off[-1]) > int(ln.sum()):                   # the entries copy offsets[n] bytes out of these buffers
+            raise FsgpuError("offsets[n] lies beyond the sequence data")
+        return bufs, off, lens
+
+    def diag_rescore(self, qAA, q3Di, mat3Di, matAA, pairs, offsets=None, lengths=None):
+        """fsgpu_diag_rescore called directly.  qAA / q3Di: lists of code arrays (0..20), one per query; mat3Di / matAA: int16 [21, 21]; pairs: DIAG_PAIR_DT
+        array or a list of (query, target, diagonal) with targets of the resident DB.  Returns a DIAG_RES_DT array, one record per pair."""
+        (qa, q3), off, lens = self._pack_seqs((qAA, q3Di), offsets, lengths)
+        m3 = np.ascontiguousarray(mat3Di, np.int16)
+        mA = np.ascontiguousarray(matAA, np.int16)
+        if m3.size != 21 * 21 or mA.size != 21 * 21:
+            raise FsgpuError("diag_rescore: matrices must be int16 [21, 21]")
+        if isinstance(pairs, np.ndarray) and pairs.dtype == DIAG_PAIR_DT:
+            p = np.ascontiguousarray(pairs)
+        else:
+            p = np.zeros(len(pairs), DIAG_PAIR_DT)
+            for k, (q, t, d) in enumerate(pairs):
+                p[k] = (int(q) & 0xFFFFFFFF, int(t) & 0xFFFFFFFF, int(d))
+        out = np.zeros(max(len(p), 1), DIAG_RES_DT)
+        out["reserved"] = -1                               # the entry writes every field of every record
+        self._chk(lib().fsgpu_diag_rescore(self.h, _ptr(qa), _ptr(q3), _ptr(off), _ptr(lens), len(lens), _ptr(m3), _ptr(mA),
+                                           _ptr(p) if len(p) else None, len(p), _ptr(out)), "fsgpu_diag_rescore")
+        return out[:len(p)]
+
+    def sw_batch_seqs(self, pAAf, p3f, pAAr, p3r, tAA, t3Di, gap_open=10, gap_extend=1, offsets=None, lengths=None):
+        """fsgpu_sw_batch_seqs called directly: both directions of the structure SW of one query against EXPLICIT targets.  tAA (None with pAA* None) /
+        t3Di: lists of code arrays (0..20).  Returns (fwd, rev) as SW_DT arrays."""
+        p3f = np.ascontiguousarray(p3f, np.int16)
+        p3r = np.ascontiguousarray(p3r, np.int16)
+        pAAf = None if pAAf is None else np.ascontiguousarray(pAAf, np.int16)
+        pAAr = None if pAAr is None else np.ascontiguousarray(pAAr, np.int16)
+        (t3, ta), off, lens = self._pack_seqs((t3Di, tAA), offsets, lengths)
+        n = len(lens)
+        fwd = np.zeros(max(n, 1), SW_DT)
+        rev = np.zeros(max(n, 1), SW_DT)
+        self._chk(lib().fsgpu_sw_batch_seqs(self.h, _ptr(pAAf), _ptr(p3f), _ptr(pAAr), _ptr(p3r), p3f.shape[1], _ptr(ta), _ptr(t3), _ptr(off), _ptr(lens), n,
+                                            gap_open, gap_extend, _ptr(fwd), _ptr(rev)), "fsgpu_sw_batch_seqs")
+        return fwd[:n], rev[:n]
 
     def block_backtrace(self, tblAA, tbl3Di, letAA, let3Di, queries, tasks, gap_open=10, gap_extend=1):
         """fsgpu_block_backtrace called directly: start position + backtrace of accepted hits by the device block aligner, nothing recomputed on the
