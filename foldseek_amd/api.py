@@ -77,6 +77,13 @@ class LddtTask(C.Structure):
                 ("btOff", C.c_uint64), ("btLen", C.c_uint32), ("reserved", C.c_uint32), ("outOff", C.c_uint64)]
 
 
+class TmTask(C.Structure):
+    """fsgpu_tm_task"""
+    _fields_ = [("query", C.c_uint32), ("tLen", C.c_int32), ("tOff", C.c_uint64), ("qStart", C.c_int32), ("dbStart", C.c_int32),
+                ("btOff", C.c_uint64), ("btLen", C.c_uint32), ("scoreD8", C.c_float), ("d0Std", C.c_float), ("d0", C.c_float),
+                ("d0Search", C.c_float), ("reserved", C.c_uint32)]
+
+
 class FsgpuError(RuntimeError):
     pass
 
@@ -104,10 +111,15 @@ def lib():
         "fsgpu_block_backtrace": (i32, [vp, vp, vp, vp, vp, C.POINTER(BtQuery), i32, C.POINTER(BtTask), i32, i32, i32, C.POINTER(BtRes), C.POINTER(C.c_void_p)]),
         "fsgpu_block_backtrace_footprint": (i32, [vp, i32]),
         "fsgpu_lddt_batch": (i32, [vp, C.POINTER(LddtQuery), i32, C.POINTER(LddtTask), i32, vp, u64, vp, u64, vp, vp, u64]),
+        "fsgpu_tm_batch": (i32, [vp, C.POINTER(LddtQuery), i32, C.POINTER(TmTask), i32, vp, u64, vp, u64, vp, vp, vp]),
+        "fshost_tm_params": (None, [i32, vp]),
+        "fshost_tm_finish": (f64, [i32, f32, f32, i32]),
+        "fshost_tm_normalization": (i32, [i32, i32, i32, i32]),
         "fshost_ca_decode": (i32, [vp, C.c_size_t, i32, vp]),
         "fshost_lddt_average": (f64, [vp, i32, C.POINTER(i32)]),
         "fshost_search_bind_ca": (i32, [vp, f32, vp, vp, vp]),
         "fshost_search_set_query_ca": (i32, [vp, i32, vp, vp]),
+        "fshost_search_set_tm": (i32, [vp, f32, i32, i32]),
         "fsgpu_gapless_plan_items": (i64, [vp, C.c_uint32, i32, f64, vp, u64, vp]),
         "fsgpu_db_broadcast": (i32, [vp, C.POINTER(vp), i32, C.POINTER(i32)]),
         "fsgpu_rccl_selfcheck": (i32, [vp]),
@@ -199,7 +211,7 @@ def exported_symbols():
             "fsgpu_db_adopt_device", "fsgpu_db_size", "fsgpu_db_residues", "fsgpu_gapless_scan", "fsgpu_gapless_scores",
             "fsgpu_gapless_launch", "fsgpu_gapless_finish", "fsgpu_sw_batch", "fsgpu_sw_multi", "fsgpu_sw_multi_dir", "fsgpu_sw_multi_dir_c", "fsgpu_sw_multi_c", "fsgpu_sw_launch", "fsgpu_sw_finish",
             "fsgpu_db_broadcast", "fsgpu_rccl_selfcheck", "fsgpu_device_count", "fsgpu_live_devices", "fsgpu_gapless_plan_items", "fsgpu_block_backtrace", "fsgpu_block_backtrace_footprint",
-            "fsgpu_lddt_batch", "fsgpu_last_kernel_ms", "fsgpu_sw_last_passes", "fsgpu_kmer_index_build", "fsgpu_kmer_index_entries", "fsgpu_kmer_search",
+            "fsgpu_lddt_batch", "fsgpu_tm_batch", "fsgpu_last_kernel_ms", "fsgpu_sw_last_passes", "fsgpu_kmer_index_build", "fsgpu_kmer_index_entries", "fsgpu_kmer_search",
             "fsgpu_kmer_index_copy", "fsgpu_kmer_row_copy", "fsgpu_kmer_last_counts", "fsgpu_kmer_last_segments", "fsgpu_kmer_plan_coarse", "fsgpu_kmer_batch_hint",
             "fsgpu_diag_rescore", "fsgpu_sw_batch_seqs"]
 
@@ -691,6 +703,39 @@ class Context:
         self._chk(lib().fsgpu_lddt_batch(self.h, qs, nq, ts, nt, _ptr(tc), tc.size, _ptr(bt), bt.size, _ptr(aln), _ptr(out), ooff), "fsgpu_lddt_batch")
         return [(int(aln[k]), out[ts[k].outOff:ts[k].outOff + max(int(aln[k]), 0)].copy()) for k in range(nt)]
 
+    def tm_batch(self, queries, targets, tasks, params=None):
+        """fsgpu_tm_batch called directly: the raw values of the reference's approximate TM-score for a batch of hits.  queries / targets: lists of
+        float32 arrays [3, L]; tasks: list of (query, target, qStart, dbStart, backtrace string, normalisation length).  The per-task scalars come from
+        fshost_tm_params.  Returns one (pairs, score_max of standard_TMscore's search, score_max of detailed_search_standard's, rmsd) per task, the
+        three floats as numpy float32; tm_finish turns them into the TM-score.  params: per task four floats in place of fshost_tm_params' (tests)."""
+        nq, nt = len(queries), len(tasks)
+        qs, keep = (LddtQuery * max(nq, 1))(), []
+        for i, q in enumerate(queries):
+            q = np.ascontiguousarray(q, np.float32)
+            if q.ndim != 2 or q.shape[0] != 3:
+                raise FsgpuError(f"tm_batch: query {i}: coordinates must be float32 [3, L]")
+            keep.append(q)
+            qs[i].ca, qs[i].L, qs[i].reserved = q.ctypes.data, q.shape[1], 0
+        tl = [np.ascontiguousarray(t, np.float32) for t in targets]
+        toff = np.concatenate([[0], np.cumsum([t.size for t in tl])]).astype(np.int64)
+        tc = np.concatenate([t.reshape(-1) for t in tl]) if tl else np.zeros(0, np.float32)
+        bts = [str(t[4]).encode() for t in tasks]
+        ts = (TmTask * max(nt, 1))()
+        boff, par = 0, {}
+        for k, (q, t, qs0, ds0, _, norm_len) in enumerate(tasks):
+            ts[k].query, ts[k].tLen, ts[k].tOff, ts[k].qStart, ts[k].dbStart = int(q), tl[int(t)].shape[1], int(toff[int(t)]), int(qs0), int(ds0)
+            ts[k].btOff, ts[k].btLen, ts[k].reserved = boff, len(bts[k]), 0
+            if norm_len not in par:
+                par[norm_len] = tm_params(norm_len)
+            ts[k].scoreD8, ts[k].d0Std, ts[k].d0, ts[k].d0Search = (float(v) for v in (params[k] if params is not None else par[norm_len]))
+            boff += len(bts[k])
+        bt = np.frombuffer(b"".join(bts), np.uint8) if boff else np.zeros(0, np.uint8)
+        n = np.full(max(nt, 1), -1, np.int32)
+        scores = np.full(2 * max(nt, 1), np.nan, np.float32)
+        rmsd = np.full(max(nt, 1), np.nan, np.float32)
+        self._chk(lib().fsgpu_tm_batch(self.h, qs, nq, ts, nt, _ptr(tc), tc.size, _ptr(bt), bt.size, _ptr(n), _ptr(scores), _ptr(rmsd)), "fsgpu_tm_batch")
+        return [(int(n[k]), scores[k], scores[nt + k], rmsd[k]) for k in range(nt)]
+
     def block_backtrace_footprint(self, workgroups_per_cu):
         """workgroups of the block aligner per compute unit for the following block_backtrace calls (0: the default)"""
         self._chk(lib().fsgpu_block_backtrace_footprint(self.h, int(workgroups_per_cu)), "fsgpu_block_backtrace_footprint")
@@ -916,3 +961,20 @@ def lddt_average(cols):
     n = C.c_int(0)
     avg = lib().fshost_lddt_average(_ptr(c), len(c), C.byref(n))
     return avg, n.value
+
+
+def tm_params(norm_len):
+    """fshost_tm_params: (score_d8, d0 of standard_TMscore, d0, d0_search) for a normalisation length, float32 [4]"""
+    out = np.zeros(4, np.float32)
+    lib().fshost_tm_params(int(norm_len), _ptr(out))
+    return out
+
+
+def tm_finish(pairs, s1, s2, norm_len):
+    """fshost_tm_finish: the TM-score (a double) from the raw values Context.tm_batch returns"""
+    return lib().fshost_tm_finish(int(pairs), float(np.float32(s1)), float(np.float32(s2)), int(norm_len))
+
+
+def tm_normalization(mode, alignment_len, query_len, target_len):
+    """fshost_tm_normalization (TMaligner::normalization)"""
+    return lib().fshost_tm_normalization(int(mode), int(alignment_len), int(query_len), int(target_len))

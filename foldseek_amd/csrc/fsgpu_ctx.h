@@ -146,6 +146,13 @@ struct fsgpu_ctx {
     std::vector<float> ldNormQuery;             // single-query calls (the one-by-one path of structurealign): the coordinates whose norms ldNorm holds, empty = none
     std::vector<uint32_t> ldOrder, ldCounts;
     std::vector<uint64_t> ldColOff;
+    // fsgpu_tm_batch (k_tm.hpp): [query coordinates | target coordinates | backtraces | descriptors], gathered pairs, the masks of hits too long for LDS,
+    // [scores and rmsd | pair counts]; the workspaces only grow; device ms of the last call's two kernels
+    DevBuf tmIn, tmPairs, tmMasks, tmOut;
+    PinBuf hTmIn, hTmOut;
+    hipEvent_t tmEv[3] = {nullptr, nullptr, nullptr};
+    double tmMs[2] = {-1, -1};
+    std::vector<uint32_t> tmCounts;
     struct {
         bool pending = false;
         int n = 0, L = 0, go = 0, ge = 0;

@@ -105,9 +105,11 @@ const FlagSpec kUngappedFlags[] = {            // Parameters::ungappedprefilter 
     {nullptr, false, USE, nullptr}};
 
 const FlagSpec kAlignFlags[] = {               // LocalParameters::structurealign = structurealign + Parameters::align
-    {"--tmscore-threshold", false, ONLY, "0|0.0|0.000"}, {"--tmscore-threshold-mode", false, IGNORE, nullptr},
-    {"--lddt-threshold", false, USE, nullptr},  // structurealign / search: LDDT on the device (k_lddt.hpp); structurerescorediagonal refuses a non-zero value itself
-    {"--alignment-type", false, ONLY, "0|2"}, {"--exact-tmscore", false, IGNORE, nullptr},
+    // structurealign / search: TM-score and LDDT on the device (k_tm.hpp, k_lddt.hpp) when both C-alpha databases exist (CaBinding);
+    // structurerescorediagonal refuses non-zero thresholds itself.  --exact-tmscore 1 is refused by CaBinding whenever a TM-score would be computed.
+    {"--tmscore-threshold", false, USE, nullptr}, {"--tmscore-threshold-mode", false, USE, nullptr},
+    {"--lddt-threshold", false, USE, nullptr},
+    {"--alignment-type", false, ONLY, "0|2"}, {"--exact-tmscore", false, USE, nullptr},
     {"-a", true, USE, "0"}, {"--add-backtrace", true, USE, "0"}, {"--alignment-mode", false, ONLY, "0|3"},
     {"--alignment-output-mode", false, ONLY, "0"}, {"--wrapped-scoring", true, ONLY, "0"}, {"-e", false, USE, nullptr},
     {"--min-seq-id", false, USE, nullptr}, {"--min-aln-len", false, USE, nullptr}, {"--seq-id-mode", false, USE, nullptr},
@@ -136,7 +138,7 @@ const FlagSpec kConvertFlags[] = {             // LocalParameters::convertalignm
     {"--format-mode", false, ONLY, "0|2|4"},   // 1 SAM and 3 HTML end in "Not implemented yet" / need the C-alpha DB in the reference too; 5 superposed PDB needs it
     {"--format-output", false, USE, nullptr}, {"--translation-table", false, IGNORE, nullptr}, {"--gap-open", false, IGNORE, nullptr},
     {"--gap-extend", false, IGNORE, nullptr}, {"--db-output", true, USE, "0"}, {"--search-type", false, IGNORE, nullptr},
-    {"--exact-tmscore", false, IGNORE, nullptr}, {nullptr, false, USE, nullptr}};
+    {"--exact-tmscore", false, USE, nullptr}, {nullptr, false, USE, nullptr}};          // refused with a TM column, without effect otherwise
 
 const FlagSpec kIndexdbFlags[] = {             // Parameters::indexdb (Parameters.cpp:850-872)
     {"--seed-sub-mat", false, ONLY, "3di.out"}, {"-k", false, ONLY, "0|6"}, {"--alph-size", false, ONLY, "21"},
@@ -417,36 +419,49 @@ bool checkMaxSeqLen(const Options &o, const DbReader &r, const std::string &what
 }
 
 // --sort-by-structure-bits 1 (default of the workflow) rescales scores by TM-score x LDDT and needs both C-alpha DBs
-// (structurealign.cpp:182-197): without them the reference warns and turns it off -- so do we; WITH them the rescoring
-// would run, which this path does not implement: refuse.
-bool resolveStructureBits(const Options &o, const std::string &qdb, const std::string &tdb, std::string &err) {
-    if (o.geti("--sort-by-structure-bits", 1) == 0) return true;
+// (structurealign.cpp:182-197): without them the reference warns and turns it off -- so do we; with them it is on (CaBinding).
+bool resolveStructureBits(const Options &o, const std::string &qdb, const std::string &tdb) {
+    if (o.geti("--sort-by-structure-bits", 1) == 0) return false;
     auto exists = [](const std::string &p) { FILE *f = fopen(p.c_str(), "rb"); if (f) fclose(f); return f != nullptr; };
-    if (exists(qdb + "_ca.dbtype") && exists(tdb + "_ca.dbtype")) {
-        err = "structurealign: --sort-by-structure-bits 1 with C-alpha databases (TM-score / LDDT rescoring) is not implemented on the device path; pass --sort-by-structure-bits 0";
-        return false;
-    }
+    if (exists(qdb + "_ca.dbtype") && exists(tdb + "_ca.dbtype")) return true;
     fprintf(stderr, "Cannot find %s C-alpha or %s C-alpha database\nDisabling --sort-by-structure-bits\n", qdb.c_str(), tdb.c_str());
-    return true;
+    return false;
 }
 
-// --lddt-threshold T > 0 (structurealign.cpp:177-250): both C-alpha databases are needed; without one of them the reference prints two warning
-// lines and carries on without the filter -- so do we.  Target entries are looked up by KEY: a padded target's _ca is keyed by the padded ids
+// --lddt-threshold T > 0, --tmscore-threshold T > 0 and structure bits (structurealign.cpp:177-250): both C-alpha databases are needed.  Without one
+// of them the reference prints two warning lines per threshold and carries on without the filter: so do we for --lddt-threshold, while
+// --tmscore-threshold > 0 keeps the refusal this path always gave there (README).  --exact-tmscore 1 is refused whenever a TM-score would be
+// computed: the device computes the approximate score only.  Target entries are looked up by KEY: a padded target's _ca is keyed by the padded ids
 // (F/data/makepaddeddb.sh:39-41), like its AA database in loadPadded; through an index target the _ca lives inside <db>.idx (user keys 500 / 501).
 struct CaBinding {
     DbReader q, tOwn;
     const DbReader *t = nullptr;
     std::vector<uint64_t> tOff;             // by target index, relative to t->dataBase()
     std::vector<uint32_t> tLen;
-    float thr = 0.0f;
+    float thr = 0.0f, tmThr = 0.0f;
+    int tmMode = 0;
+    bool structBits = false;
     bool on = false;
-    bool open(const Options &o, const std::string &qdb, const std::string &tdb, bool sameDB, const PaddedTarget &pt, std::string &err) {
+    bool open(const Options &o, const char *module, bool structureBits, const std::string &qdb, const std::string &tdb, bool sameDB, const PaddedTarget &pt,
+              std::string &err) {
         thr = (float) o.getd("--lddt-threshold", 0.0);
-        if (!(thr > 0.0f)) return true;
-        if (!DbReader::caExists(qdb) || !DbReader::caExists(tdb)) {
-            fprintf(stderr, "Cannot use --lddt-threshold with --sort-by-structure-bits 0\nDisabling --lddt-threshold\n");
+        tmThr = (float) o.getd("--tmscore-threshold", 0.0);
+        tmMode = o.geti("--tmscore-threshold-mode", 0);
+        structBits = structureBits;
+        const bool haveCa = DbReader::caExists(qdb) && DbReader::caExists(tdb);
+        if (!structBits && !haveCa) {
+            if (tmThr > 0.0f) {
+                err = std::string(module) + ": --tmscore-threshold " + o.kv.at("--tmscore-threshold") + " is not implemented on the device path (supported: 0|0.0|0.000)";
+                return false;
+            }
+            if (thr > 0.0f) fprintf(stderr, "Cannot use --lddt-threshold with --sort-by-structure-bits 0\nDisabling --lddt-threshold\n");
             return true;
         }
+        if ((tmThr > 0.0f || structBits) && o.geti("--exact-tmscore", 0) != 0) {
+            err = std::string(module) + ": --exact-tmscore 1 is not implemented on the device path (supported: 0)";
+            return false;
+        }
+        if (!(thr > 0.0f) && !(tmThr > 0.0f) && !structBits) return true;
         if (!q.openCa(qdb, err)) return false;
         if (sameDB) t = &q;
         else { if (!tOwn.openCa(tdb, err)) return false; t = &tOwn; }
@@ -460,7 +475,10 @@ struct CaBinding {
         on = true;
         return true;
     }
-    bool bind(fshost_search *s) const { return !on || fshost_search_bind_ca(s, thr, t->dataBase(), tOff.data(), tLen.data()) == FSGPU_OK; }
+    bool bind(fshost_search *s) const {
+        return !on || (fshost_search_set_tm(s, tmThr, tmMode, structBits ? 1 : 0) == FSGPU_OK &&
+                       fshost_search_bind_ca(s, thr, t->dataBase(), tOff.data(), tLen.data()) == FSGPU_OK);
+    }
     // the C-alpha entry of a query key for fshost_search_set_query_ca
     bool queryEntry(uint32_t key, const char *&entry, uint32_t &len) const {
         const int64_t id = q.idOf(key);
@@ -1009,7 +1027,7 @@ int fsmod_search(int argc, const char **argv) {
     par.prefCompBiasScale = (float) o.getd("--comp-bias-corr-scale", 0.15);    // StructureSearch.cpp:101
     par.alnCompBiasScale = 0.5f;                                               // StructureSearch.cpp:107
     const int kmerThr = o.geti("--k-score", INT_MAX) != INT_MAX ? o.geti("--k-score", 0) : fshost_kmer_threshold((float) o.getd("-s", 9.5), 6);
-    if (!resolveStructureBits(o, o.pos[0], o.pos[1], err)) return fail(err);
+    const bool structBits = resolveStructureBits(o, o.pos[0], o.pos[1]);
     if (!checkMaxSeqLen(o, q3, "query", err) || !checkMaxSeqLen(o, t3, "target", err)) return fail(err);
     const int spaced = o.geti("--spaced-kmer-mode", 1);
     if (prefMode == 0 && (o.geti("-k", 0) != 0 && o.geti("-k", 6) != 6)) return fail("search: only -k 6 is implemented on the device path");
@@ -1021,7 +1039,7 @@ int fsmod_search(int argc, const char **argv) {
     PaddedTarget pt;
     if (!loadPadded(t3, &tA, m3, &mA, pt, err)) return fail(err);
     CaBinding ca;
-    if (!ca.open(o, o.pos[0], o.pos[1], sameDB, pt, err)) return fail(err);
+    if (!ca.open(o, "search", structBits, o.pos[0], o.pos[1], sameDB, pt, err)) return fail(err);
     const double tLoaded = nowSec();
     DeviceSet ds;
     if (!ds.open(o, pt, true, 3, err, true)) { ds.close(); return fail(err); }
@@ -1249,7 +1267,7 @@ int fsmod_structurealign(int argc, const char **argv) {
     fshost_params par;
     fillParams(o, par);
     par.alnCompBiasScale = (float) o.getd("--comp-bias-corr-scale", 0.5);
-    if (!resolveStructureBits(o, o.pos[0], o.pos[1], err)) return fail(err);
+    const bool structBits = resolveStructureBits(o, o.pos[0], o.pos[1]);
     if (!checkMaxSeqLen(o, q3, "query", err) || !checkMaxSeqLen(o, t3, "target", err)) return fail(err);
     Matrix m3, mA;
     m3.builtin(FSHOST_MAT_3DI, 2.1f, 0.0f);
@@ -1257,7 +1275,7 @@ int fsmod_structurealign(int argc, const char **argv) {
     PaddedTarget pt;
     if (!loadPadded(t3, &tA, m3, &mA, pt, err)) return fail(err);
     CaBinding ca;
-    if (!ca.open(o, o.pos[0], o.pos[1], sameDB, pt, err)) return fail(err);
+    if (!ca.open(o, "structurealign", structBits, o.pos[0], o.pos[1], sameDB, pt, err)) return fail(err);
     DeviceSet ds;
     if (!ds.open(o, pt, true, 3, err, true)) { ds.close(); return fail(err); }
     DbWriter w;
@@ -1365,6 +1383,8 @@ int fsmod_structurerescorediagonal(int argc, const char **argv) {
     if (o.geti("--alt-ali", 0) != 0) return fail("structurerescorediagonal: --alt-ali is not read by this module");
     if (o.getd("--lddt-threshold", 0.0) != 0.0)
         return fail("structurerescorediagonal: --lddt-threshold " + o.kv["--lddt-threshold"] + " is not implemented on the device path (supported: 0)");
+    if (o.getd("--tmscore-threshold", 0.0) != 0.0)
+        return fail("structurerescorediagonal: --tmscore-threshold " + o.kv["--tmscore-threshold"] + " is not implemented on the device path (supported: 0|0.0|0.000)");
     std::string err;
     DbReader qA, q3, tA, t3, pref;
     if (!qA.open(o.pos[0], err) || !q3.open(dbPathWithSuffix(o.pos[0], "_ss"), err) || !tA.open(o.pos[1], err) || !t3.open(dbPathWithSuffix(o.pos[1], "_ss"), err) ||
@@ -1868,15 +1888,15 @@ int fsmod_gpuserver(int argc, const char **argv) {
 // ---- convertalis -------------------------------------------------------------------------------------------------
 // F/src/strucclustutils/structureconvertalis.cpp:253-1445 for the BLAST-tab family (--format-mode 0, 2, 4) and every
 // --format-output column that is a function of the alignment record, the sequences and the headers.  Columns computed from
-// C-alpha coordinates other than LDDT (alntmscore, qtmscore, ttmscore, rmsd, u, t, qca, tca), taxonomy and multimer
-// columns are refused by name.  lddt / lddtfull (:660-680,770-773,1095-1107) are answered by the device entry fsgpu_lddt_batch: a context is
-// opened only when one of the two is asked for, and without <db>_ca they are refused like the others.  `prob` only reads the score (CalcProbTP.h), so it is answered without the _ca DB the reference
+// the superposition or the raw coordinates (u, t, qca, tca), taxonomy and multimer columns are refused by name.  lddt / lddtfull
+// (:660-680,770-773,1095-1107) are answered by the device entry fsgpu_lddt_batch, alntmscore / qtmscore / ttmscore / rmsd (:1074-1094) by
+// fsgpu_tm_batch: a context is opened only when one of them is asked for, and without <db>_ca they are refused like the others.  `prob` only reads the score (CalcProbTP.h), so it is answered without the _ca DB the reference
 // insists on opening for it.
 namespace {
 
 enum ConvCol { C_QUERY, C_TARGET, C_QKEY, C_TKEY, C_EVALUE, C_GAPOPEN, C_PIDENT, C_FIDENT, C_NIDENT, C_QSTART, C_QEND, C_QLEN, C_TSTART, C_TEND,
                C_TLEN, C_ALNLEN, C_BITS, C_CIGAR, C_QSEQ, C_TSEQ, C_Q3DI, C_T3DI, C_QHEADER, C_THEADER, C_QALN, C_TALN, C_Q3DIALN, C_T3DIALN,
-               C_MISMATCH, C_QCOV, C_TCOV, C_EMPTY, C_PROB, C_QSET, C_QSETID, C_TSET, C_TSETID, C_LDDT, C_LDDTFULL };
+               C_MISMATCH, C_QCOV, C_TCOV, C_EMPTY, C_PROB, C_QSET, C_QSETID, C_TSET, C_TSETID, C_LDDT, C_LDDTFULL, C_ALNTM, C_QTM, C_TTM, C_RMSD };
 
 struct ConvColSpec { const char *name; ConvCol col; bool needSeq, need3Di, needBt; int needSets = 0; };   // needSets: 1 = .lookup, 2 = .source
 const ConvColSpec kConvCols[] = {        // LocalParameters::getOutputFormat (LocalParameters.cpp:464-553)
@@ -1893,8 +1913,9 @@ const ConvColSpec kConvCols[] = {        // LocalParameters::getOutputFormat (Lo
     {"qset", C_QSET, false, false, false, 3}, {"qsetid", C_QSETID, false, false, false, 3}, {"tset", C_TSET, false, false, false, 1},
     {"tsetid", C_TSETID, false, false, false, 3},
     // backtrace columns; the query length comes from the sequence database, as in the reference (:663-664)
-    {"lddt", C_LDDT, true, false, true}, {"lddtfull", C_LDDTFULL, true, false, true}};
-const char *const kConvRefused[] = {"qca", "tca", "u", "t", "alntmscore", "qtmscore", "ttmscore", "rmsd",
+    {"lddt", C_LDDT, true, false, true}, {"lddtfull", C_LDDTFULL, true, false, true},
+    {"alntmscore", C_ALNTM, true, false, true}, {"qtmscore", C_QTM, true, false, true}, {"ttmscore", C_TTM, true, false, true}, {"rmsd", C_RMSD, true, false, true}};
+const char *const kConvRefused[] = {"qca", "tca", "u", "t",
                                     "taxid", "taxname", "taxlineage", "complexqtmscore", "multimerqtmscore", "complexttmscore", "multimerttmscore",
                                     "complexassignid", "multimerassignid", "complexu", "multimeru", "complext", "multimert", "qcomplexcoverage",
                                     "qmultimercoverage", "tcomplexcoverage", "tmultimercoverage", "qchaintms", "tchaintms", "qchains", "tchains", "interfacelddt"};
@@ -2025,7 +2046,9 @@ struct ConvLddt {
     std::vector<int32_t> scoreLen;
     std::vector<uint64_t> off;
     std::vector<float> cols;
-    void clear() { avg.clear(); scoreLen.clear(); off.clear(); cols.clear(); }
+    // TM-scores per record for the normalisations asked for (0 alntmscore, 1 qtmscore, 2 ttmscore) and the rmsd
+    std::vector<double> tm[3], rmsd;
+    void clear() { avg.clear(); scoreLen.clear(); off.clear(); cols.clear(); rmsd.clear(); for (auto &v : tm) v.clear(); }
 };
 struct ConvLddtRun {
     fsgpu_ctx *ctx = nullptr;
@@ -2038,6 +2061,12 @@ struct ConvLddtRun {
     // entries order[oi0 .. oi1) of the alignment DB: one device call
     bool chunk(const DbReader &aln, const std::vector<size_t> &order, size_t oi0, size_t oi1, const DbReader &qSeq, const DbReader &qCa, const DbReader &tCa,
                bool keepCols, ConvLddt &out, std::string &err);
+    bool wantLddt = true;
+    bool wantTm[3] = {false, false, false}, wantRmsd = false;          // which TM columns: one device task per (record, requested normalisation)
+    std::vector<int> normLens;                                           // [record][3]
+    std::vector<fsgpu_tm_task> tmTasks;
+    std::vector<int32_t> tmPairs;
+    std::vector<float> tmScores, tmRmsd;
     std::vector<std::vector<float>> qCoords;
     std::vector<fsgpu_lddt_query> queries;
     std::vector<fsgpu_lddt_task> tasks;
@@ -2049,13 +2078,44 @@ struct ConvLddtRun {
 bool ConvLddtRun::chunk(const DbReader &aln, const std::vector<size_t> &order, size_t oi0, size_t oi1, const DbReader &qSeq, const DbReader &qCa,
                         const DbReader &tCa, bool keepCols, ConvLddt &out, std::string &err) {
     out.clear();
-    qCoords.clear(); tasks.clear(); tCoords.clear(); tWhere.clear(); bts.clear();
+    qCoords.clear(); tasks.clear(); tCoords.clear(); tWhere.clear(); bts.clear(); normLens.clear();
     uint64_t outOff = 0;
     bool ok = true;
     auto flush = [&]() {
         if (tasks.empty()) return true;
         queries.resize(qCoords.size());
         for (size_t i = 0; i < qCoords.size(); i++) { queries[i].ca = qCoords[i].data(); queries[i].L = (int32_t) (qCoords[i].size() / 3); queries[i].reserved = 0; }
+        // the rmsd does not depend on the normalisation: it is read from the first task of its record (the reference asks with the target length)
+        bool norm[3] = {wantTm[0], wantTm[1], wantTm[2]};
+        if (wantRmsd && !norm[0] && !norm[1] && !norm[2]) norm[2] = true;
+        if (norm[0] || norm[1] || norm[2]) {
+            tmTasks.clear();
+            for (size_t t = 0; t < tasks.size(); t++)
+                for (int m = 0; m < 3; m++) {
+                    if (!norm[m]) continue;
+                    fsgpu_tm_task k;
+                    k.query = tasks[t].query; k.tLen = tasks[t].tLen; k.tOff = tasks[t].tOff; k.qStart = tasks[t].qStart; k.dbStart = tasks[t].dbStart;
+                    k.btOff = tasks[t].btOff; k.btLen = tasks[t].btLen; k.reserved = 0;
+                    float par[4];
+                    fshost_tm_params(normLens[3 * t + m], par);
+                    k.scoreD8 = par[0]; k.d0Std = par[1]; k.d0 = par[2]; k.d0Search = par[3];
+                    tmTasks.push_back(k);
+                }
+            const size_t nt = tmTasks.size();
+            tmPairs.resize(nt); tmScores.resize(2 * nt); tmRmsd.resize(nt);
+            if (fsgpu_tm_batch(ctx, queries.data(), (int) queries.size(), tmTasks.data(), (int) nt, tCoords.data(), tCoords.size(), bts.data(), bts.size(),
+                               tmPairs.data(), tmScores.data(), tmRmsd.data()) != FSGPU_OK) { err = std::string("convertalis: ") + fsgpu_last_error(ctx); return false; }
+            size_t k = 0;
+            for (size_t t = 0; t < tasks.size(); t++) {
+                out.rmsd.push_back((double) tmRmsd[k]);
+                for (int m = 0; m < 3; m++) {
+                    if (!norm[m]) { out.tm[m].push_back(0.0); continue; }
+                    out.tm[m].push_back(fshost_tm_finish(tmPairs[k], tmScores[k], tmScores[nt + k], normLens[3 * t + m]));
+                    k++;
+                }
+            }
+        }
+        if (!wantLddt) { out.avg.resize(tasks.size(), 0.0); return true; }          // avg counts the records of the chunk either way
         lens.resize(tasks.size()); colBuf.resize(std::max<uint64_t>(outOff, 1));
         if (fsgpu_lddt_batch(ctx, queries.data(), (int) queries.size(), tasks.data(), (int) tasks.size(), tCoords.data(), tCoords.size(), bts.data(), bts.size(),
                              lens.data(), colBuf.data(), outOff) != FSGPU_OK) { err = std::string("convertalis: ") + fsgpu_last_error(ctx); return false; }
@@ -2105,6 +2165,7 @@ bool ConvLddtRun::chunk(const DbReader &aln, const std::vector<size_t> &order, s
             bts += bt;
             outOff += (uint64_t) std::count(bt.begin(), bt.end(), 'M');
             tasks.push_back(t);
+            normLens.push_back(std::min(res.qEnd - res.qStart, res.dbEnd - res.dbStart)); normLens.push_back(Lq); normLens.push_back(res.dbLen);
         }
     }
     return ok && flush();
@@ -2148,7 +2209,9 @@ extern "C" int fsmod_convertalis(int argc, const char **argv) {
         if (name.empty()) continue;
         const ConvColSpec *spec = nullptr;
         for (const ConvColSpec &c : kConvCols) if (name == c.name) spec = &c;
-        if (!spec) {
+        const bool tmCol = spec && (spec->col == C_ALNTM || spec->col == C_QTM || spec->col == C_TTM || spec->col == C_RMSD);
+        if (!spec || (tmCol && (!DbReader::caExists(o.pos[0]) || !DbReader::caExists(o.pos[1])))) {
+            if (tmCol) return fail("convertalis: column " + name + " is not implemented on this path (needs the C-alpha, taxonomy or multimer data)");
             for (const char *r : kConvRefused)
                 if (name == r) return fail("convertalis: column " + name + " is not implemented on this path (needs the C-alpha, taxonomy or multimer data)");
             return fail("Format code " + name + " does not exist.");
@@ -2168,7 +2231,8 @@ extern "C" int fsmod_convertalis(int argc, const char **argv) {
     const bool sameDB = o.pos[0] == o.pos[1];
     std::string err;
     std::string lddtCol;
-    for (size_t c = 0; c < cols.size(); c++) if ((cols[c] == C_LDDT || cols[c] == C_LDDTFULL) && lddtCol.empty()) lddtCol = colNames[c];
+    // (the name of the first column that needs C-alpha coordinates: LDDT or TM-score)
+    for (size_t c = 0; c < cols.size(); c++) if (cols[c] >= C_LDDT && cols[c] <= C_RMSD && lddtCol.empty()) lddtCol = colNames[c];
     if (!lddtCol.empty() && format == 2) lddtCol.clear();          // --format-mode 2 prints its fixed columns
     if (!lddtCol.empty() && (!DbReader::caExists(o.pos[0]) || !DbReader::caExists(o.pos[1])))
         return fail("convertalis: column " + lddtCol + " is not implemented on this path for databases without C-alpha coordinates (no <db>_ca)");
@@ -2207,6 +2271,14 @@ extern "C" int fsmod_convertalis(int argc, const char **argv) {
     ConvLddtRun lddtRun;
     bool wantLddtFull = false;
     for (ConvCol c : cols) wantLddtFull = wantLddtFull || c == C_LDDTFULL;
+    lddtRun.wantLddt = false;
+    for (ConvCol c : cols) {
+        lddtRun.wantLddt = lddtRun.wantLddt || c == C_LDDT || c == C_LDDTFULL;
+        if (c == C_ALNTM || c == C_QTM || c == C_TTM) lddtRun.wantTm[c - C_ALNTM] = true;
+        lddtRun.wantRmsd = lddtRun.wantRmsd || c == C_RMSD;
+    }
+    if (!lddtCol.empty() && o.geti("--exact-tmscore", 0) != 0 && (lddtRun.wantRmsd || lddtRun.wantTm[0] || lddtRun.wantTm[1] || lddtRun.wantTm[2]))
+        return fail("convertalis: --exact-tmscore 1 is not implemented on the device path (supported: 0)");
     if (!lddtCol.empty()) {
         if (!qCa.openCa(o.pos[0], err) || (!sameDB && !tCaOwn.openCa(o.pos[1], err))) return fail(err);
         if (!lddtRun.open(o.geti("--gpu-device", 0), err)) return fail(err);
@@ -2363,6 +2435,8 @@ extern "C" int fsmod_convertalis(int argc, const char **argv) {
                     case C_TSET: result += tSetToSource[tKeyToSet[res.dbKey]]; break;
                     case C_TSETID: result += std::to_string(tKeyToSet[res.dbKey]); break;
                     case C_LDDT: appendE3(result, lddt.avg[rec]); break;
+                    case C_ALNTM: case C_QTM: case C_TTM: appendE3(result, lddt.tm[cols[c] - C_ALNTM][rec]); break;
+                    case C_RMSD: appendE3(result, lddt.rmsd[rec]); break;
                     case C_LDDTFULL: {
                         // the first scoreLength per-column values, NaN shown as 0 (:1099-1107).  With no scored column the reference prints the float in front
                         // of its empty array: 0.000 in the frozen output

@@ -24,7 +24,8 @@
 using namespace fsh;
 
 // one hit whose LDDT is wanted: query index of the call, target index, start cells, backtrace
-struct LddtJob { int q; uint32_t tid; int qStart, dbStart; const std::string *bt; };
+// (normLen: the TM-score's normalisation length, TMaligner::normalization of the hit)
+struct LddtJob { int q; uint32_t tid; int qStart, dbStart; const std::string *bt; int normLen = 0; };
 
 struct fshost_search {
     fsgpu_ctx *ctx = nullptr;
@@ -71,7 +72,19 @@ struct fshost_search {
     std::vector<size_t> ldWhere;
     std::vector<double> ldAvg;
     std::vector<LddtJob> ldJobs;
-    bool lddtOn() const { return lddtThr > 0.0f && tCaBase != nullptr; }
+    // TM-score filter and structure bits (fshost_search_set_tm): --tmscore-threshold, --tmscore-threshold-mode, --sort-by-structure-bits; staging of a
+    // fsgpu_tm_batch call.  Structure bits need both values of every accepted hit, whatever the thresholds (structurealign.cpp:209-214).
+    float tmThr = 0.0f;
+    int tmMode = 0;
+    bool structBits = false;
+    std::vector<fsgpu_tm_task> tmTasks;
+    std::vector<int32_t> tmPairs;
+    std::vector<float> tmScores, tmRmsd;
+    std::vector<double> tmVal;
+    bool tmWanted() const { return tmThr > 0.0f || structBits; }
+    bool lddtOn() const { return (lddtThr > 0.0f || structBits) && tCaBase != nullptr; }
+    bool tmOn() const { return tmWanted() && tCaBase != nullptr; }
+    bool caOn() const { return lddtOn() || tmOn(); }
     // host-side wall time of the last calls, seconds: [0] prefilter profile, [1] prefilter device call (incl. wait),
     // [2] align profiles + e-value net, [3] SW device call (incl. wait), [4] gates, [5] block-aligner backtrace
     double stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -224,9 +237,14 @@ void fshost_search_free(fshost_search *s) { delete s; }
 
 int fshost_search_bind_ca(fshost_search *s, float lddtThr, const char *caBase, const uint64_t *caOffsets, const uint32_t *caLengths) {
     if (!s) return FSGPU_E_ARG;
-    if (!(lddtThr > 0.0f) || !caBase) { s->lddtThr = 0.0f; s->tCaBase = nullptr; s->tCaOff = nullptr; s->tCaLen = nullptr; return FSGPU_OK; }
+    if ((!(lddtThr > 0.0f) && !s->tmWanted()) || !caBase) { s->lddtThr = 0.0f; s->tCaBase = nullptr; s->tCaOff = nullptr; s->tCaLen = nullptr; return FSGPU_OK; }
     if (!caOffsets || !caLengths) { s->err = "fshost_search_bind_ca: offsets and lengths are required"; return FSGPU_E_ARG; }
-    s->lddtThr = lddtThr; s->tCaBase = caBase; s->tCaOff = caOffsets; s->tCaLen = caLengths;
+    s->lddtThr = lddtThr > 0.0f ? lddtThr : 0.0f; s->tCaBase = caBase; s->tCaOff = caOffsets; s->tCaLen = caLengths;
+    return FSGPU_OK;
+}
+int fshost_search_set_tm(fshost_search *s, float tmThr, int mode, int structureBits) {
+    if (!s || mode < 0 || mode > 2) return FSGPU_E_ARG;
+    s->tmThr = tmThr > 0.0f ? tmThr : 0.0f; s->tmMode = mode; s->structBits = structureBits != 0;
     return FSGPU_OK;
 }
 int fshost_search_set_query_ca(fshost_search *s, int nq, const char *const *entries, const uint32_t *lengths) {
@@ -521,7 +539,7 @@ int lddtPrepareQueries(fshost_search *s, AlignQuery *aq, int nq) {
     std::vector<uint32_t> &lens = s->ldQLen;
     entries.swap(s->qCaEntry); lens.swap(s->qCaLen);          // consumed by this call
     s->qCaEntry.clear(); s->qCaLen.clear();
-    if (!s->lddtOn()) return FSGPU_OK;
+    if (!s->caOn()) return FSGPU_OK;
     if ((int) entries.size() != nq) { s->err = "the LDDT filter is bound but the query C-alpha entries of this call were not set (fshost_search_set_query_ca)"; return FSGPU_E_ARG; }
     if ((int) s->qCa.size() < nq) s->qCa.resize(nq);
     std::atomic<int> bad{-1};
@@ -535,8 +553,10 @@ int lddtPrepareQueries(fshost_search *s, AlignQuery *aq, int nq) {
 }
 // avg[j] = LDDTScoreResult::avgLddtScore of job j: target entries decoded on the host pool (once per distinct target), all-pairs part on the device,
 // ordered average on the host
-int lddtJobs(fshost_search *s, const AlignQuery *aq, int nq, const std::vector<LddtJob> &jobs, std::vector<double> &avg) {
+// tm[j] = the TM-score of job j (fsgpu_tm_batch on the same staging, scalars and scalings on the host), when the handle asks for it
+int lddtJobs(fshost_search *s, const AlignQuery *aq, int nq, const std::vector<LddtJob> &jobs, std::vector<double> &avg, std::vector<double> &tm) {
     avg.assign(jobs.size(), 0.0);
+    tm.assign(jobs.size(), 0.0);
     if (jobs.empty()) return FSGPU_OK;
     std::vector<uint32_t> &tids = s->ldTids;
     tids.resize(jobs.size());
@@ -567,6 +587,22 @@ int lddtJobs(fshost_search *s, const AlignQuery *aq, int nq, const std::vector<L
         s->ldBt.append(*job.bt);
         outOff += (uint64_t) std::count(job.bt->begin(), job.bt->end(), 'M');
     }
+    if (s->tmOn()) {
+        s->tmTasks.resize(jobs.size()); s->tmPairs.resize(jobs.size()); s->tmScores.resize(2 * jobs.size()); s->tmRmsd.resize(jobs.size());
+        for (size_t j = 0; j < jobs.size(); j++) {
+            const fsgpu_lddt_task &l = s->ldTasks[j];
+            fsgpu_tm_task &t = s->tmTasks[j];
+            t.query = l.query; t.tLen = l.tLen; t.tOff = l.tOff; t.qStart = l.qStart; t.dbStart = l.dbStart; t.btOff = l.btOff; t.btLen = l.btLen; t.reserved = 0;
+            float par[4];
+            fshost_tm_params(jobs[j].normLen, par);
+            t.scoreD8 = par[0]; t.d0Std = par[1]; t.d0 = par[2]; t.d0Search = par[3];
+        }
+        const int rc = fsgpu_tm_batch(s->ctx, s->ldQ.data(), nq, s->tmTasks.data(), (int) jobs.size(), s->ldT.data(), s->ldT.size(), s->ldBt.data(), s->ldBt.size(),
+                                      s->tmPairs.data(), s->tmScores.data(), s->tmRmsd.data());
+        if (rc != FSGPU_OK) { s->err = fsgpu_last_error(s->ctx); return rc; }
+        for (size_t j = 0; j < jobs.size(); j++) tm[j] = fshost_tm_finish(s->tmPairs[j], s->tmScores[j], s->tmScores[jobs.size() + j], jobs[j].normLen);
+    }
+    if (!s->lddtOn()) return FSGPU_OK;
     s->ldOut.resize(std::max<uint64_t>(outOff, 1));
     const int rc = fsgpu_lddt_batch(s->ctx, s->ldQ.data(), nq, s->ldTasks.data(), (int) jobs.size(), s->ldT.data(), s->ldT.size(), s->ldBt.data(), s->ldBt.size(),
                                     s->ldLen.data(), s->ldOut.data(), outOff);
@@ -575,11 +611,22 @@ int lddtJobs(fshost_search *s, const AlignQuery *aq, int nq, const std::vector<L
     return FSGPU_OK;
 }
 
+// TMaligner::normalization of a hit (structurealign.cpp:391): no + 1 on the spans
+int tmNormLen(const fshost_search *s, const fshost_result &r) {
+    return fshost_tm_normalization(s->tmMode, std::min(r.qEndPos - r.qStartPos, r.dbEndPos - r.dbStartPos), (int) r.qLen, (int) r.dbLen);
+}
+// structurealign.cpp:21-29
+bool compareHitsByStructureBits(const fshost_result &first, const fshost_result &second) {
+    if (first.score != second.score) return first.score > second.score;
+    if (first.dbLen != second.dbLen) return first.dbLen < second.dbLen;
+    return first.dbKey < second.dbKey;
+}
+
 // alignStructure gates + backtrace + checkCriteria + ordering for one query (structurealign.cpp:37-112,350-445).
 // pre / preIdx: backtraces computed ahead by the worker pool (preIdx[k] = index into pre, -1 = none); without them the
 // backtrace of a pair is computed here, when the loop reaches it (the --max-accept / --max-rejected path).
 int gateAlign(fshost_search *s, const AlignQuery &aq, int64_t identityId, const uint32_t *targetIds, int n, const fsgpu_swres *fwd,
-              const fsgpu_swres *rev, fshost_result *results, double &tBack, const BlockAlnOut *pre, const int *preIdx, const double *preLddt = nullptr) {
+              const fsgpu_swres *rev, fshost_result *results, double &tBack, const BlockAlnOut *pre, const int *preIdx, const double *preLddt = nullptr, const double *preTm = nullptr) {
     const fshost_params &par = s->par;
     const int resCap = n * (1 + std::max(0, par.altAlignment));
     int passedNum = 0, rejected = 0, nres = 0;
@@ -611,19 +658,27 @@ int gateAlign(fshost_search *s, const AlignQuery &aq, int64_t identityId, const 
         const bool accepted = fillResult(s, aq, tid, f, score, evalue, bo, isIdentity, r);
         r.backtraceOff = (uint32_t) s->cigars.size();
         if (accepted) {
-            if (s->lddtOn()) {
-                // structurealign.cpp:398-408: the hit is dropped by a bare `continue` -- it counts neither as accepted nor as rejected
-                double avg;
-                if (preLddt && pre && preIdx && preIdx[k] >= 0) avg = preLddt[preIdx[k]];
-                else if (!bo.ok || bo.backtrace.empty()) avg = fshost_lddt_average(nullptr, 0, nullptr);      // no aligned column: the reference's 0 / 0
+            if (s->caOn()) {
+                // structurealign.cpp:382-410: a hit below a threshold is dropped by a bare `continue` -- it counts neither as accepted nor as rejected;
+                // the TM-score is tested before the LDDT (NaN and inf compare false and are kept)
+                const int normLen = tmNormLen(s, r);
+                double avg, tm;
+                if (!bo.ok || bo.backtrace.empty()) {               // no aligned column: the reference's 0 / 0, and its score_max of -1 over no pair
+                    avg = fshost_lddt_average(nullptr, 0, nullptr);
+                    tm = fshost_tm_finish(0, -1.0f, -1.0f, normLen);
+                } else if (preLddt && preTm && pre && preIdx && preIdx[k] >= 0) { avg = preLddt[preIdx[k]]; tm = preTm[preIdx[k]]; }
                 else {
-                    s->ldJobs.assign(1, LddtJob{0, tid, bo.qStart, bo.dbStart, &bo.backtrace});
-                    const int rc = lddtJobs(s, &aq, 1, s->ldJobs, s->ldAvg);
+                    s->ldJobs.assign(1, LddtJob{0, tid, bo.qStart, bo.dbStart, &bo.backtrace, normLen});
+                    const int rc = lddtJobs(s, &aq, 1, s->ldJobs, s->ldAvg, s->tmVal);
                     if (rc != FSGPU_OK) return rc;
-                    avg = s->ldAvg[0];
+                    avg = s->ldAvg[0]; tm = s->tmVal[0];
                 }
-                if (avg < (double) s->lddtThr) continue;
-                r.dbcov = (float) avg;
+                if (s->tmOn() && tm < (double) s->tmThr) continue;
+                if (s->lddtOn()) {
+                    if (avg < (double) s->lddtThr) continue;
+                    r.dbcov = (float) avg;
+                }
+                if (s->structBits && s->tmOn() && s->lddtOn()) r.score = (int32_t) (r.score * sqrt(avg * tm));
             }
             s->cigars.append(bo.backtrace);
             s->cigars.push_back('\0');
@@ -638,7 +693,10 @@ int gateAlign(fshost_search *s, const AlignQuery &aq, int64_t identityId, const 
             rejected++;
         }
     }
-    if (nres > 1) std::sort(results, results + nres, compareHits);
+    if (nres > 1) {
+        if (s->structBits && s->caOn()) std::sort(results, results + nres, compareHitsByStructureBits);
+        else std::sort(results, results + nres, compareHits);
+    }
     return nres;
 }
 
@@ -823,9 +881,9 @@ void precomputeBacktraces(const fshost_search *s, const std::vector<AlignQuery> 
 // (the reference computes LDDT only after it, structurealign.cpp:376-398).  lddt[index into pb.outs]; a hit without backtrace keeps the 0 / 0 the
 // reference computes for it.
 int lddtPrecomputed(fshost_search *s, const AlignQuery *aq, int nq, const int64_t *identityId, const uint32_t *const *targetIds, const int *n,
-                    const fsgpu_swres *fwd, const fsgpu_swres *rev, const PreBacktrace &pb, std::vector<double> &lddt) {
-    lddt.clear();
-    if (!s->lddtOn() || pb.outs.empty()) return FSGPU_OK;
+                    const fsgpu_swres *fwd, const fsgpu_swres *rev, const PreBacktrace &pb, std::vector<double> &lddt, std::vector<double> &tm) {
+    lddt.clear(); tm.clear();
+    if (!s->caOn() || pb.outs.empty()) return FSGPU_OK;
     std::vector<LddtJob> &jobs = s->ldJobs;
     std::vector<size_t> &where = s->ldWhere;
     jobs.clear(); where.clear();
@@ -839,15 +897,17 @@ int lddtPrecomputed(fshost_search *s, const AlignQuery *aq, int nq, const int64_
             fshost_result r;
             if (!passesScoreGates(s, aq[i], tid, fwd[base + k], rev[base + k], score, evalue, nullptr)) continue;
             if (!fillResult(s, aq[i], tid, fwd[base + k], score, evalue, pb.outs[o], identityId && (int64_t) tid == identityId[i], r)) continue;
-            jobs.push_back(LddtJob{i, tid, pb.outs[o].qStart, pb.outs[o].dbStart, &pb.outs[o].backtrace});
+            jobs.push_back(LddtJob{i, tid, pb.outs[o].qStart, pb.outs[o].dbStart, &pb.outs[o].backtrace, tmNormLen(s, r)});
             where.push_back((size_t) o);
         }
         base += (size_t) n[i];
     }
-    const int rc = lddtJobs(s, aq, nq, jobs, s->ldAvg);
+    const int rc = lddtJobs(s, aq, nq, jobs, s->ldAvg, s->tmVal);
     if (rc != FSGPU_OK) return rc;
+    // a hit without backtrace is not a job: gateAlign computes its 0 / 0 and its pairless TM-score itself (it never reads these slots for such a hit)
     lddt.assign(pb.outs.size(), fshost_lddt_average(nullptr, 0, nullptr));
-    for (size_t j = 0; j < jobs.size(); j++) lddt[where[j]] = s->ldAvg[j];
+    tm.assign(pb.outs.size(), 0.0);
+    for (size_t j = 0; j < jobs.size(); j++) { lddt[where[j]] = s->ldAvg[j]; tm[where[j]] = s->tmVal[j]; }
     return FSGPU_OK;
 }
 
@@ -882,10 +942,10 @@ int fshost_search_align(fshost_search *s, const uint8_t *qAA, const uint8_t *q3d
         aq = std::move(one[0]);
     }
     tBack += pb.seconds;
-    std::vector<double> preLddt;
-    if ((rc = lddtPrecomputed(s, &aq, 1, &identityId, &targetIds, &n, s->fwd.data(), s->rev.data(), pb, preLddt)) != FSGPU_OK) return rc;
+    std::vector<double> preLddt, preTm;
+    if ((rc = lddtPrecomputed(s, &aq, 1, &identityId, &targetIds, &n, s->fwd.data(), s->rev.data(), pb, preLddt, preTm)) != FSGPU_OK) return rc;
     const int nres = gateAlign(s, aq, identityId, targetIds, n, s->fwd.data(), s->rev.data(), results, tBack, pb.outs.data(), pb.idx[0].empty() ? nullptr : pb.idx[0].data(),
-                               preLddt.empty() ? nullptr : preLddt.data());
+                               preLddt.empty() ? nullptr : preLddt.data(), preTm.empty() ? nullptr : preTm.data());
     s->stats[2] = t1 - t0; s->stats[3] = t2 - t1; s->stats[5] = tBack; s->stats[4] = nowSec() - t2 - tBack;
     return nres;
 }
@@ -979,12 +1039,12 @@ int fshost_search_align_batch(fshost_search *s, int nq, const uint8_t *const *qA
     PreBacktrace pb;
     precomputeBacktraces(s, aq, targetIds, n, s->fwd.data(), s->rev.data(), pb);
     tBack += pb.seconds;
-    std::vector<double> preLddt;
-    if ((rc = lddtPrecomputed(s, aq.data(), nq, identityId, targetIds, n, s->fwd.data(), s->rev.data(), pb, preLddt)) != FSGPU_OK) return rc;
+    std::vector<double> preLddt, preTm;
+    if ((rc = lddtPrecomputed(s, aq.data(), nq, identityId, targetIds, n, s->fwd.data(), s->rev.data(), pb, preLddt, preTm)) != FSGPU_OK) return rc;
     size_t base = 0;
     for (int i = 0; i < nq; i++) {
         nres[i] = gateAlign(s, aq[i], identityId ? identityId[i] : -1, targetIds[i], n[i], s->fwd.data() + base, s->rev.data() + base, results[i], tBack,
-                            pb.outs.data(), pb.idx[i].empty() ? nullptr : pb.idx[i].data(), preLddt.empty() ? nullptr : preLddt.data());
+                            pb.outs.data(), pb.idx[i].empty() ? nullptr : pb.idx[i].data(), preLddt.empty() ? nullptr : preLddt.data(), preTm.empty() ? nullptr : preTm.data());
         if (nres[i] < 0) return nres[i];
         base += (size_t) n[i];
     }
@@ -1060,7 +1120,7 @@ int fshost_search_kmer_batch(fshost_search *s, const fshost_matrix *mKmer, const
     t0 = t1;
     if (!lq.empty()) {
         lres.assign(lq.size(), 0);
-        if (s->lddtOn() && (int) s->qCaEntry.size() == nq) {          // the C-alpha entries of the queries that reach the aligner, in its order
+        if (s->caOn() && (int) s->qCaEntry.size() == nq) {          // the C-alpha entries of the queries that reach the aligner, in its order
             std::vector<const char *> e(lq.size()); std::vector<uint32_t> l(lq.size());
             for (size_t j = 0; j < lq.size(); j++) { e[j] = s->qCaEntry[lq[j]]; l[j] = s->qCaLen[lq[j]]; }
             s->qCaEntry.swap(e); s->qCaLen.swap(l);

@@ -26,6 +26,7 @@
  *   fsgpu_sw_multi / _multi_dir       the same for a batch of queries, one device launch per register class and direction
  *                                     (forward over all pairs, reversed over the pairs alignStructure still needs:
  *                                     F/src/strucclustutils/structurealign.cpp:50-65)
+ *   fsgpu_tm_batch                    TMaligner::computeAppoximateTMscore                               F/src/commons/TMaligner.cpp:50-104, F/lib/tmalign
  *   fsgpu_lddt_batch                  LDDTCalculator::initQuery / computeLDDTScore                      F/src/commons/LDDT.cpp:87-215, call sites
  *                                     F/src/strucclustutils/structurealign.cpp:331-341,398-408, structureconvertalis.cpp:770-773
  *   fsgpu_db_broadcast                replication of the resident DB over the GPUs of a node (RCCL), SURVEY 8e
@@ -295,6 +296,32 @@ typedef struct {
 int fsgpu_lddt_batch(fsgpu_ctx *ctx, const fsgpu_lddt_query *queries, int nq, const fsgpu_lddt_task *tasks, int nt, const float *tCoords, uint64_t tCoordsLen,
                      const char *bt, uint64_t btBytes, int32_t *alignLength, float *out, uint64_t outCap);
 
+/* ---- TM-score of accepted hits: TMaligner::computeTMscore with computeExactScore == false (F/src/commons/TMaligner.cpp:50-104, F/lib/tmalign) ------------
+ * Per task the device pairs the residues along the backtrace ('M' pairs, 'I' advances the query, every other character the target), runs the two
+ * fragment searches of computeAppoximateTMscore (standard_TMscore's and detailed_search_standard's TMscore8_search_standard, simplify_step 40) and the
+ * KabschFast over all pairs, and returns raw values: nPairs[k], scores[k] / scores[nt + k] = the float score_max of the two searches (-1 without pairs),
+ * rmsd[k].  All of it bit for bit what the reference computes, except where the double-precision atan2 / cos / sin of the device library differ from
+ * the host's in the last place AND the difference survives the cast to float.  The scalars that need pow() and the final scalings are the
+ * host's, with the C library the reference uses: fshost_tm_params fills the five floats of a task from its normalisation length, fshost_tm_finish
+ * turns the raw values into the TM-score.  The rotation and translation are not returned.
+ * Queries, tCoords, bt and the task geometry as for fsgpu_lddt_batch.  Alignments of any length up to FSGPU_MAX_SEQ_LEN run on the device; there is no
+ * host path. */
+typedef struct {
+    uint32_t query;         /* index into queries */
+    int32_t tLen;           /* residues of the target */
+    uint64_t tOff;          /* float offset of its coordinates in tCoords */
+    int32_t qStart, dbStart;
+    uint64_t btOff;
+    uint32_t btLen;
+    float scoreD8;          /* parameter_set4search: score_d8 */
+    float d0Std;            /* standard_TMscore: its d0, which is also its local_d0_search */
+    float d0;               /* parameter_set4search: d0 (= D0_MIN) */
+    float d0Search;         /* parameter_set4search: d0_search */
+    uint32_t reserved;
+} fsgpu_tm_task;
+int fsgpu_tm_batch(fsgpu_ctx *ctx, const fsgpu_lddt_query *queries, int nq, const fsgpu_tm_task *tasks, int nt, const float *tCoords, uint64_t tCoordsLen,
+                   const char *bt, uint64_t btBytes, int32_t *nPairs, float *scores, float *rmsd);
+
 /* ---- prefilter: k-mer matching with double-diagonal hits + ungapped diagonal scoring ------------------------- */
 /* Index parameters == the subset of Prefiltering's members that shape IndexTable / SequenceLookup.  Sequence-
  * sequence searches with k = 6 only (what setupSplit picks below 3.35e9 residues, IndexTable.h:456-458). */
@@ -392,7 +419,8 @@ int fsgpu_kmer_plan_coarse(const int32_t *lengths, uint64_t n, uint32_t blocksPe
  * which = 0 gapless scan kernel, 1 SW kernel, 2 whole device part of the last fsgpu_kmer_search batch,
  * 3..10 its stages (similar-k-mer count, index probes, hit gather, partition into (query, bin) segments, double-diagonal
  * detection per segment, scoring, replay, selection), 11 host tail, 12 the index-probe kernel (k_kmer_lists) alone,
- * 14 / 15 the two kernels of the last fsgpu_lddt_batch (k_lddt_norm, k_lddt_pairs).
+ * 14 / 15 the two kernels of the last fsgpu_lddt_batch (k_lddt_norm, k_lddt_pairs),
+ * 16 / 17 the two kernels of the last fsgpu_tm_batch (k_tm_pairs, k_tm_search).
  * Returns < 0 if nothing was recorded. */
 double fsgpu_last_kernel_ms(const fsgpu_ctx *ctx, int which);
 /* out[2][4], per direction (0 forward, 1 reversed query) of the last fsgpu_sw_multi_dir calls of this context: device ms of that pass's

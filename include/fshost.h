@@ -217,6 +217,15 @@ int fshost_ca_decode(const char *entry, size_t entryLen, int L, float *out);
 /* LDDTScoreResult (LDDT.h:102-119) over the per-column values fsgpu_lddt_batch returns: NaN columns are skipped and reduce *scoreLength, the float sum runs
  * in column order, the result is (double) (sum / (float) scoreLength) -- 0 / 0 with the sign the x86 reference produces when every column is NaN. */
 double fshost_lddt_average(const float *cols, int alignLength, int *scoreLength);
+/* The host half of the TM-score (fsgpu_tm_batch), computed with this machine's C library as the reference does.
+ * fshost_tm_params: parameter_set4search(normLen, normLen) and the d0 of standard_TMscore (TMalign.cpp:25-47,1371-1378) ->
+ * out[0] score_d8, out[1] standard_TMscore's d0 (also its local_d0_search), out[2] d0, out[3] d0_search: the four floats of a fsgpu_tm_task.
+ * fshost_tm_finish: TMscore = max((float) (s2 * nPairs / (float) normLen), (double) s1 * nPairs / (1.0 * normLen)) for the raw score_max s1 of
+ * standard_TMscore's search and s2 of detailed_search_standard's (TMalign.cpp:1423,622; TMaligner.cpp:102).
+ * fshost_tm_normalization: TMaligner::normalization(mode, alignmentLen, queryLen, targetLen), mode 0 alignment, 1 query, 2 target; 0 for any other mode. */
+void fshost_tm_params(int normLen, float out[4]);
+double fshost_tm_finish(int nPairs, float s1, float s2, int normLen);
+int fshost_tm_normalization(int mode, int alignmentLen, int queryLen, int targetLen);
 /* Binds C-alpha data and --lddt-threshold to a search handle (structurealign.cpp:177-250,331-341,376-411): with lddtThr > 0 every hit that passes
  * Alignment::checkCriteria has its LDDT computed on the device (one fsgpu_lddt_batch per align batch) and is dropped -- neither accepted nor rejected --
  * when the average is below the threshold; alternative alignments (--alt-ali) are not filtered.  Target entry i (target INDEX, as for `keys`) is
@@ -225,6 +234,13 @@ double fshost_lddt_average(const float *cols, int alignLength, int *scoreLength)
  * / lengths[q] for the queries of that call in their order (borrowed until it returns; consumed by it).  A bound handle refuses an align call without them. */
 int fshost_search_bind_ca(fshost_search *s, float lddtThr, const char *caBase, const uint64_t *caOffsets, const uint32_t *caLengths);
 int fshost_search_set_query_ca(fshost_search *s, int nq, const char *const *entries, const uint32_t *lengths);
+/* --tmscore-threshold, --tmscore-threshold-mode (0 alignment, 1 query, 2 target; anything else is refused) and --sort-by-structure-bits for a search handle
+ * (structurealign.cpp:209-226,382-445); call it BEFORE fshost_search_bind_ca, which keeps the binding when either is set even with lddtThr <= 0.  With
+ * tmThr > 0 every hit that passes Alignment::checkCriteria has its TM-score computed on the device (one fsgpu_tm_batch per align batch, next to the LDDT
+ * call) and is dropped -- neither accepted nor rejected -- when it is below the threshold, before the LDDT test.  With structureBits both values are
+ * computed for every such hit whatever the thresholds, score = (int) (score * sqrt(avgLddt * tm)), dbcov = avgLddt, and the hits of a query are ordered
+ * by score descending, dbLen ascending, dbKey ascending.  Alternative alignments keep their own scores.  Without bound C-alpha data neither has an effect. */
+int fshost_search_set_tm(fshost_search *s, float tmThr, int mode, int structureBits);
 
 /* text formats: QueryMatcher::prefilterHitToBuffer (QueryMatcher.h:120-132), Matcher::resultToBuffer (Matcher.cpp:282) */
 size_t fshost_format_prefilter_hit(char *buf, uint32_t key, int score, int diagonal);
