@@ -42,6 +42,11 @@ class KmerQuery(C.Structure):
                 ("reserved", C.c_int32), ("identity", C.c_int64)]
 
 
+class GaplessQuery(C.Structure):
+    """fsgpu_gapless_query"""
+    _fields_ = [("pssm", C.c_void_p), ("L", C.c_int32), ("scoreCap", C.c_int32), ("identityId", C.c_int64)]
+
+
 KMER_HIT_DT = np.dtype([("id", np.uint32), ("score", np.int32), ("diag", np.uint16), ("pad", np.uint16)])
 SW_DT = SWRES_DT      # fsgpu_swres under the name the oracle bindings use
 DIAG_PAIR_DT = np.dtype([("query", np.uint32), ("target", np.uint32), ("diagonal", np.int32)])      # fsgpu_diag_pair
@@ -384,6 +389,23 @@ class Context:
         self._chk(lib().fsgpu_gapless_scan(self.h, _ptr(pssm), pssm.shape[1], cap, min_score, identity, max_res, _ptr(out),
                                            C.byref(nout)), "fsgpu_gapless_scan")
         return out[:nout.value]
+
+    def gapless_scan_multi(self, queries, min_score=30, max_res=1000):
+        """fsgpu_gapless_scan_multi called directly.  queries: list of (pssm int8 [21, L], cap, identity); a pssm of None goes down as a null
+        profile of length 1.  Returns one hit array per query; gapless_scores_multi(i) then reads query i's score vector."""
+        nq = len(queries)
+        keep, arr = [], (GaplessQuery * max(nq, 1))()
+        for i, (pssm, cap, identity) in enumerate(queries):
+            p = None if pssm is None else np.ascontiguousarray(pssm, np.int8)
+            buf = None if p is None else (p if p.size else np.zeros(1, np.int8))       # L = 0 still carries a pointer: the entry refuses the length
+            keep.append(buf)
+            arr[i].pssm = None if buf is None else buf.ctypes.data
+            arr[i].L, arr[i].scoreCap, arr[i].identityId = (1 if p is None else p.shape[1]), int(cap), int(identity)
+        out = np.zeros(max(1, nq * max_res), HIT_DT)
+        nout = np.zeros(max(nq, 1), np.int32)
+        self._chk(lib().fsgpu_gapless_scan_multi(self.h, C.cast(arr, C.c_void_p), nq, min_score, max_res, _ptr(out), _ptr(nout)),
+                  "fsgpu_gapless_scan_multi")
+        return [out[i * max_res:i * max_res + nout[i]].copy() for i in range(nq)]
 
     # ---- k-mer prefilter ------------------------------------------------------------------------------------
     def kmer_index_build(self, kmer_matrix, kmer_thr=78, kmer_size=6, spaced=1, mask_lower_case=1, mask_n_repeats=6):
