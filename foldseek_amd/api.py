@@ -142,6 +142,7 @@ def lib():
         "fsgpu_sw_finish": (i32, [vp, vp, vp]),
         "fsgpu_last_kernel_ms": (f64, [vp, i32]),
         "fsgpu_sw_last_passes": (None, [vp, vp]),
+        "fsgpu_sw3_last_plan": (None, [vp, vp]),
         "fsgpu_kmer_index_build": (i32, [vp, vp, vp]),
         "fsgpu_kmer_index_entries": (u64, [vp]),
         "fsgpu_kmer_search": (i32, [vp, vp, vp, i32, vp, vp, vp, vp]),
@@ -216,7 +217,7 @@ def exported_symbols():
             "fsgpu_db_adopt_device", "fsgpu_db_size", "fsgpu_db_residues", "fsgpu_gapless_scan", "fsgpu_gapless_scores",
             "fsgpu_gapless_launch", "fsgpu_gapless_finish", "fsgpu_sw_batch", "fsgpu_sw_multi", "fsgpu_sw_multi_dir", "fsgpu_sw_multi_dir_c", "fsgpu_sw_multi_c", "fsgpu_sw_launch", "fsgpu_sw_finish",
             "fsgpu_db_broadcast", "fsgpu_rccl_selfcheck", "fsgpu_device_count", "fsgpu_live_devices", "fsgpu_gapless_plan_items", "fsgpu_block_backtrace", "fsgpu_block_backtrace_footprint",
-            "fsgpu_lddt_batch", "fsgpu_tm_batch", "fsgpu_last_kernel_ms", "fsgpu_sw_last_passes", "fsgpu_kmer_index_build", "fsgpu_kmer_index_entries", "fsgpu_kmer_search",
+            "fsgpu_lddt_batch", "fsgpu_tm_batch", "fsgpu_last_kernel_ms", "fsgpu_sw_last_passes", "fsgpu_sw3_last_plan", "fsgpu_kmer_index_build", "fsgpu_kmer_index_entries", "fsgpu_kmer_search",
             "fsgpu_kmer_index_copy", "fsgpu_kmer_row_copy", "fsgpu_kmer_last_counts", "fsgpu_kmer_last_segments", "fsgpu_kmer_plan_coarse", "fsgpu_kmer_batch_hint",
             "fsgpu_diag_rescore", "fsgpu_sw_batch_seqs"]
 
@@ -770,6 +771,16 @@ class Context:
         out = np.zeros(8)
         lib().fsgpu_sw_last_passes(self.h, _ptr(out))
         return out.reshape(2, 4)
+
+    def sw3_last_plan(self):
+        """what the last compact SW call (sw_multi_dir_c / sw_multi_c) planned and ran (fsgpu_sw3_last_plan): pairs and rows-per-lane classes per
+        shape (lanes per target pair -> count / set of R), pairs on the profile path, pairs re-run in int32, images built, launch groups, workgroups"""
+        o = np.zeros(12, np.uint32)
+        lib().fsgpu_sw3_last_plan(self.h, _ptr(o))
+        o = [int(v) for v in o]
+        return {"pairs": {16: o[0], 32: o[1], 64: o[2]},
+                "classes": {hl: {r for r in range(32) if o[3 + k] >> r & 1} for k, hl in enumerate((16, 32, 64))},
+                "profile_pairs": o[6], "rerun_pairs": o[7], "images_built": o[8], "groups": o[9], "workgroups": o[10]}
 
     def close(self):
         if getattr(self, "h", None):

@@ -213,7 +213,7 @@ static int mqSlots(fsgpu_ctx *ctx, MqBatch &b) {
 // Short queries (<= 256 residues) of one 16-row class run two to a kernel (k_gapless<2R, false, PAIRED>: the per-column
 // instructions that do not scale with the rows are shared); an odd one out runs alone.
 static void mqPairShort(fsgpu_ctx *ctx, MqBatch &b) {
-    // classes up to 16 registers (256 residues): beyond that the pair would need the 6-wave workgroups of R > 36, which was measured
+    // classes up to 16 registers (256 residues): beyond that the pair would need the 8-wave workgroups of R > 36, which was measured
     // and loses (pairs up to class 20 / 24 / 28 at 1M targets: 2.74 / 2.77 / 2.84 ms per query against 2.76 without)
     constexpr int pairMaxR = kGaplessMaxR / 2;
     GaplessQuery *rec = (GaplessQuery *) ctx->hMqRec.p;

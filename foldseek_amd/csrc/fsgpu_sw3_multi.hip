@@ -246,6 +246,7 @@ static int sw3Images(fsgpu_ctx *ctx, const Sw3Plan &p) {
                              (uint32_t *) ctx->s3img.p, hasAA, p.S);
     if (rc != FSGPU_OK) return rc;
     ctx->s3Sig = sig;
+    ctx->s3Plan[8] = (uint32_t) nImg;
     return FSGPU_OK;
 }
 
@@ -278,6 +279,18 @@ static void sw3Groups(Sw3Plan &p) {
         p.nBlocks += g.nblk;
         p.groups.push_back(g);
     }
+}
+
+// the view of the plan that fsgpu_sw3_last_plan hands out: counters only, nothing here feeds a launch
+static void sw3RecordPlan(fsgpu_ctx *ctx, const Sw3Plan &p) {
+    uint32_t *o = ctx->s3Plan;
+    for (const Sw3Plan::Part &pt : p.parts) {
+        const int shape = pt.key / 12;
+        o[shape] += (uint32_t) pt.n;
+        o[3 + shape] |= 1u << pt.R;
+    }
+    o[9] = (uint32_t) p.groups.size();
+    o[10] = (uint32_t) p.nBlocks;
 }
 
 // target ids and workgroup descriptors of the pass, with the accounting for fsgpu_sw_last_passes; uploads both
@@ -398,6 +411,7 @@ static int sw3RerunSaturated(fsgpu_ctx *ctx, const Sw3Plan &p) {
             if (out[p.base[i] + j].score == 32767 || (p.dir == 2 && out2[p.base[i] + j].score == 32767)) { ids.push_back(q[i].targetIds[j]); where.push_back(j); }
         }
         if (ids.empty()) continue;
+        ctx->s3Plan[7] += (uint32_t) ids.size();
         Sw3Prof pr;
         p.profilesOf(i, pr);
         f2.resize(ids.size()); r2.resize(ids.size());
@@ -432,7 +446,9 @@ static int sw3MultiImpl(fsgpu_ctx *ctx, const int8_t *mat3Di, const int8_t *matA
         fsgpu_ctx *c; hipStream_t s; bool ok = false;
         ~Drain() { if (ok) return; (void) hipStreamSynchronize(s); for (int i = 0; i < fsgpu_ctx::kSwAux; i++) if (c->swAux[i]) (void) hipStreamSynchronize(c->swAux[i]); (void) hipGetLastError(); }
     } drain{ctx, p.S};
+    memset(ctx->s3Plan, 0, sizeof(ctx->s3Plan));
     if ((rc = sw3Classic(ctx, p)) != FSGPU_OK) return rc;
+    for (int i : p.classic) ctx->s3Plan[6] += (uint32_t) p.nSelAll(i);
     p.sbase.assign(nq + 1, 0);
     for (int i = 0; i < nq; i++) p.sbase[i + 1] = p.sbase[i] + (size_t) p.nSel(i);
     p.total = p.sbase[nq];
@@ -453,6 +469,7 @@ static int sw3MultiImpl(fsgpu_ctx *ctx, const int8_t *mat3Di, const int8_t *matA
     sw3SortAndSplit(ctx, p);
     if ((rc = sw3Images(ctx, p)) != FSGPU_OK) return rc;
     sw3Groups(p);
+    sw3RecordPlan(ctx, p);
     if ((rc = sw3Descriptors(ctx, p)) != FSGPU_OK) return rc;
     if ((rc = sw3Launch(ctx, p)) != FSGPU_OK) return rc;
     if ((rc = sw3Collect(ctx, p)) != FSGPU_OK) return rc;
@@ -472,6 +489,11 @@ int fsgpu_sw_multi_dir_c(fsgpu_ctx *ctx, const int8_t *mat3Di, const int8_t *mat
 int fsgpu_sw_multi_c(fsgpu_ctx *ctx, const int8_t *mat3Di, const int8_t *matAA, const fsgpu_sw_cquery *q, int nq, int gapOpen, int gapExtend,
                      fsgpu_swres *fwd, fsgpu_swres *rev) {
     return sw3MultiImpl(ctx, mat3Di, matAA, q, nq, gapOpen, gapExtend, 2, nullptr, nullptr, fwd, rev);
+}
+
+void fsgpu_sw3_last_plan(const fsgpu_ctx *ctx, uint32_t *out) {
+    if (!out) return;
+    for (int i = 0; i < 12; i++) out[i] = ctx ? ctx->s3Plan[i] : 0u;
 }
 
 } // extern "C"

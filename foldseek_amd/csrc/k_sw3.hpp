@@ -187,6 +187,7 @@ __device__ __forceinline__ void sw3Body(const Sw3Args &a, const SwBlockDesc &bd,
     // The striped reference kernel's F is local to a segment of segLen = ceil(L / 16) query rows (k_sw.hpp).  With 16 lanes per target pair
     // R = ceil(L / 16) IS segLen: a lane's rows are exactly one segment, its segment-local F never leaves the lane -- no mask per row, no
     // DPP move, 13 instead of 14 instructions per register row.
+    // (While gapOpen > gapExtend the segment-local F changes E but no record -- tests/sw_model.py; it is carried because the source has it.)
     constexpr bool LANESEG = HL == 16;
     uint32_t segmask[LANESEG ? 1 : R];
     if constexpr (!LANESEG) {

@@ -427,6 +427,14 @@ double fsgpu_last_kernel_ms(const fsgpu_ctx *ctx, int which);
  * k_sw2 launches (HIP events on the context stream; -1 when the pass did not run), DP cells (query rows x target columns over the
  * single-tile pairs), pairs, and the VALU wave-instructions its waves issue (DP rows + per-step overhead; the issue-rate roofline's unit). */
 void fsgpu_sw_last_passes(const fsgpu_ctx *ctx, double *out);
+/* out[12]: what the last fsgpu_sw_multi_dir_c / fsgpu_sw_multi_c call of this context planned and ran (counters kept on the host; a call that
+ * fails its argument checks leaves them as they were; one that fails later, out of memory for instance, leaves them zeroed or partly filled).  A pair counts once, also when fsgpu_sw_multi_c runs it in both directions.
+ * [0] [1] [2] pairs run by k_sw3 with 16 / 32 / 64 lanes per target pair; [3] [4] [5] for the same three shapes the rows-per-lane classes that
+ * were launched, bit R set for R rows per lane (R = 1..24 with 16 lanes, 1..16 with 32 and 64); [6] pairs of the queries of more than 1024 rows,
+ * which took the profile path; [7] pairs handed to the int32 re-run because a direction of theirs returned 32767; [8] LDS images built in this call
+ * (0: those of an earlier call over the same queries were reused, or no pair ran through k_sw3); [9] launch groups per direction; [10] workgroups per direction;
+ * [11] 0. */
+void fsgpu_sw3_last_plan(const fsgpu_ctx *ctx, uint32_t *out);
 
 #ifdef __cplusplus
 }

@@ -92,6 +92,14 @@ def test_sw3_every_class_equals_the_per_pair_kernel(env, atype, shape):
         f, r = ctx.sw_batch(pAf, p3f, pAr, p3r, ids)
         want_f.append(f); want_r.append(r)
     got_f = ctx.sw_multi_dir_c(t3, tA if use_aa else None, queries, 0)
+    plan = ctx.sw3_last_plan()
+    assert plan["profile_pairs"] == PAIRS[-1] and sum(plan["pairs"].values()) == sum(PAIRS[:-1]), plan
+    if shape == "mid896_noshort":          # the 16-lane shape forced: the odd classes up to 23 and R = 1, 2, 4, 22 of these lengths
+        in16 = {-(-len(q[1]) // 16) for q in queries if len(q[1]) <= 384 and (db.lengths[q[6].astype(np.int64)] <= 896).any()}
+        assert plan["classes"][16] == in16 and len(in16) >= 13 and not plan["classes"][32] - {13, 14, 15, 16}, plan
+    if shape == "no16_noshort":
+        in32 = {-(-len(q[1]) // 32) for q in queries if len(q[1]) <= 512 and (db.lengths[q[6].astype(np.int64)] <= 896).any()}
+        assert plan["pairs"][16] == 0 and plan["classes"][32] == in32 and len(in32) >= 14, plan
     for i, L in enumerate(LENGTHS):
         _same(got_f[i], want_f[i], (atype, "fwd", L))
     got_r = ctx.sw_multi_dir_c(t3, tA if use_aa else None, queries, 1)          # finds the forward call's images in place
@@ -201,9 +209,16 @@ def test_sw3_call_of_100k_pairs_takes_the_16_lane_shape_by_itself(env, atype, mo
     for k in ("FSGPU_SW3_MID", "FSGPU_SW3_SHORT"):
         monkeypatch.delenv(k, raising=False)
     auto_f = ctx.sw_multi_dir_c(t3, tA if use_aa else None, queries, 0)
+    # "by itself": the plan says so -- every query of up to 384 rows has pairs in the 16-lane shape, and only targets of up to 512 columns are there
+    plan = ctx.sw3_last_plan()
+    short_q = [q for q in queries if len(q[1]) <= 384]
+    assert plan["classes"][16] == {-(-len(q[1]) // 16) for q in short_q} and len(plan["classes"][16]) >= 15, plan
+    assert plan["pairs"][16] == sum(int((db.lengths[q[6].astype(np.int64)] <= 512).sum()) for q in short_q) > 20000, plan
     auto_r = ctx.sw_multi_dir_c(t3, tA if use_aa else None, queries, 1)
+    assert ctx.sw3_last_plan()["images_built"] == 0
     monkeypatch.setenv("FSGPU_SW3_MID", "0")
     off_f = ctx.sw_multi_dir_c(t3, tA if use_aa else None, queries, 0)
+    assert ctx.sw3_last_plan()["pairs"][16] == 0 and not ctx.sw3_last_plan()["classes"][16]
     off_r = ctx.sw_multi_dir_c(t3, tA if use_aa else None, queries, 1)
     for k in range(len(queries)):
         assert auto_f[k].tobytes() == off_f[k].tobytes() and auto_r[k].tobytes() == off_r[k].tobytes(), k
