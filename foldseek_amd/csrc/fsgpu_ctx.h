@@ -52,6 +52,7 @@ struct DbStore {
     // gapless work lists, one per overlap class (index = overlap in 16-column chunks, 0 = whole stripes): built on first
     // use by gaplessItems() (fsgpu_gapless.hip), shared by all contexts of this DB
     std::vector<uint32_t> hStripeLen;
+    std::vector<uint32_t> hStripeCols;   // real columns of every stripe (its longest target); hStripeLen = ceil(this / 16)
     struct ItemList { uint4 *items = nullptr; uint32_t n = 0; bool split = false, built = false; };
     ItemList itemLists[kGaplessMaxRUntiled + 1];
     std::mutex itemMutex;

@@ -57,7 +57,7 @@ static int buildDb(fsgpu_ctx *ctx, const uint8_t *dRaw3di, const uint8_t *dRawAA
     HIPCHK(hipMemcpy(ctx->db->hLengths.data(), dLen, n * sizeof(int32_t), hipMemcpyDeviceToHost));
     const uint32_t nStripes = (uint32_t) ((n + kStripeTargets - 1) / kStripeTargets);
     std::vector<uint64_t> sOff(nStripes);
-    std::vector<uint32_t> sLen(nStripes);
+    std::vector<uint32_t> sLen(nStripes), sCols(nStripes);
     uint64_t total = 0, residues = 0;
     int maxLen = 0;
     // a stripe = 8 targets of similar length: group along the length-sorted order (identity for a padded DB, which
@@ -79,11 +79,13 @@ static int buildDb(fsgpu_ctx *ctx, const uint8_t *dRaw3di, const uint8_t *dRawAA
             residues += (uint64_t) L;
         }
         maxLen = std::max(maxLen, mx);
+        sCols[s] = (uint32_t) mx;
         sLen[s] = (uint32_t) ((mx + 15) / 16);
         sOff[s] = total;
         total += (uint64_t) sLen[s] * 8;
     }
     ctx->db->hStripeLen = sLen;
+    ctx->db->hStripeCols = sCols;
 
     HIPCHK(hipMalloc((void **) &ctx->db->scan, std::max<uint64_t>(total, 1) * sizeof(uint4)));
     HIPCHK(hipMalloc((void **) &ctx->db->stripeOff, std::max<size_t>(nStripes, 1) * sizeof(uint64_t)));

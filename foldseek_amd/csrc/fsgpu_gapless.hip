@@ -72,6 +72,37 @@ extern "C" int64_t fsgpu_gapless_plan_items(const uint32_t *stripeLen, uint32_t 
     return (int64_t) v.size();
 }
 
+// Device records of planned items: {stripe, range word, stripe offset in the scan layout (uint4 units) lo, trim << 24 | offset hi}.
+// trim = real columns of the stripe's last chunk (1..16: longest target - 16 * (chunks - 1)), carried by the one item whose range ends with
+// that chunk -- for a stripe cut into column segments the last segment alone -- and 0 everywhere else.  It rides in the top byte of the
+// fourth word, which the offset (56 bits of 16-byte units left) never reaches; k_gapless masks it out where it forms the offset.
+// Pure host function, exported as fsgpu_gapless_item_records for the CPU tests.
+static bool gaplessRecords(const std::vector<uint64_t> &v, const uint32_t *len, const uint32_t *cols, uint32_t nStripes, uint4 *rec) {
+    std::vector<uint64_t> sOff(nStripes);
+    uint64_t acc = 0;
+    for (uint32_t s = 0; s < nStripes; s++) {
+        if (len[s] != (cols[s] + 15) / 16) return false;
+        sOff[s] = acc; acc += (uint64_t) len[s] * 8;
+    }
+    if (acc >> 56) return false;
+    for (size_t i = 0; i < v.size(); i++) {
+        const uint32_t st = (uint32_t) (v[i] >> 32), endChunk = (uint32_t) (v[i] & 0xffff);
+        if (st >= nStripes || endChunk > len[st]) return false;
+        const uint32_t trim = endChunk == len[st] ? cols[st] - 16 * (len[st] - 1) : 0;
+        rec[i] = make_uint4(st, (uint32_t) v[i], (uint32_t) sOff[st], (uint32_t) (sOff[st] >> 32) | (trim << 24));
+    }
+    return true;
+}
+
+extern "C" int64_t fsgpu_gapless_item_records(const uint64_t *items, uint64_t nItems, const uint32_t *stripeLen, const uint32_t *stripeCols, uint32_t nStripes, uint32_t *records) {
+    if ((!items && nItems) || ((!stripeLen || !stripeCols) && nStripes) || (!records && nItems)) return -1;
+    std::vector<uint64_t> v(items, items + nItems);
+    std::vector<uint4> rec(nItems);
+    if (!gaplessRecords(v, stripeLen, stripeCols, nStripes, rec.data())) return -1;
+    if (nItems) memcpy(records, rec.data(), nItems * sizeof(uint4));
+    return (int64_t) nItems;
+}
+
 static int gaplessItems(fsgpu_ctx *ctx, int ov, const uint4 **items, uint32_t *nItems, bool *anySplit) {
     DbStore &db = *ctx->db;
     std::lock_guard<std::mutex> lock(db.itemMutex);
@@ -83,17 +114,8 @@ static int gaplessItems(fsgpu_ctx *ctx, int ov, const uint4 **items, uint32_t *n
         bool split = false;
         uint32_t cap = 0;
         planGaplessItems(len, ov, (double) ctx->numCU * 3 * (kGaplessBlock / 64), v, split, cap);
-        // device record: {stripe, range word, stripe offset in the scan layout (uint4 units) lo, hi}
         std::vector<uint4> rec(v.size());
-        {
-            std::vector<uint64_t> sOff(nStripes);
-            uint64_t acc = 0;
-            for (uint32_t s = 0; s < nStripes; s++) { sOff[s] = acc; acc += (uint64_t) len[s] * 8; }
-            for (size_t i = 0; i < v.size(); i++) {
-                const uint32_t st = (uint32_t) (v[i] >> 32);
-                rec[i] = make_uint4(st, (uint32_t) v[i], (uint32_t) sOff[st], (uint32_t) (sOff[st] >> 32));
-            }
-        }
+        if (!gaplessRecords(v, len.data(), db.hStripeCols.data(), nStripes, rec.data())) { ctx->err = "internal: gapless work items do not fit the stripe table"; return FSGPU_E_ARG; }
         HIPCHK(hipMalloc((void **) &l.items, std::max<size_t>(rec.size(), 1) * sizeof(uint4)));
         if (!rec.empty()) {
             const hipError_t ce = hipMemcpy(l.items, rec.data(), rec.size() * sizeof(uint4), hipMemcpyHostToDevice);

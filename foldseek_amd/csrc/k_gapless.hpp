@@ -18,7 +18,12 @@
 //     target residue is (code << 8) | laneOffset: ONE v_perm_b32 straight from the packed residue word (the
 //     4-register chunks sit at immediate offsets k * 22 * 256).  LDS bytes/cell = 2.
 //   * per target column a lane issues 1.5 R DP ops + 3 others (row address, dpp, hand-off perm): measured
-//     tools/ubench/gapless_ablate.hip, profiles/r01_q_gapless_ablation_ubench.txt.
+//     tools/ubench/gapless_ablate.hip, profiles/r01_q_gapless_ablation_ubench.txt.  Exactly 1.5 R for odd R too: the last register has no
+//     partner for the max3 in its own column, so an even column keeps it and the next one folds both (gaplessColumn).
+//   * only real columns run: a stripe is stored in 16-column chunks, and of the last chunk (untiled kernels) a loop over single columns runs
+//     the `trim` columns up to the stripe's longest target, which the work item carries; the columns of dead codes behind them -- 2.1 % of
+//     all columns of the benchmark's database -- would clamp every cell to zero and leave nothing behind.  Row tiles run every padded column:
+//     their border arrays are indexed by padded column.
 //   * the target DB is pre-tiled in HBM as 8-target stripes (targets grouped by length) interleaved at 16-byte granularity: one wave-level
 //     global load = one 128-byte line, every byte of the DB is read exactly once per query.
 //   * diagonal hand-off between lanes: v_mov_b32_dpp row_shr:1 + v_perm_b32 (no LDS round trip).
@@ -85,7 +90,7 @@ struct GaplessArgs {
     const uint64_t *stripeOff;  // [nStripes] offset in uint4 units
     const uint32_t *stripeLen;  // [nStripes] length in 16-column chunks
     const uint32_t *stripeTargets; // [nStripes][8] target id per stripe slot, 0xffffffff = empty slot
-    const uint4 *items;         // [nItems] work items, longest first: {stripe, split << 31 | firstChunk << 16 | endChunk, stripe offset lo, hi}
+    const uint4 *items;         // [nItems] work items, longest first: {stripe, split << 31 | firstChunk << 16 | endChunk, stripe offset lo, trim << 24 | offset hi}
     uint32_t nItems;
     uint32_t nTargets;
     const int8_t *pssm;         // [21][L] query profile (device copy)
@@ -100,6 +105,91 @@ struct GaplessArgs {
     uint16_t *borderOut;
     int16_t *scoreAcc;          // running maximum over tiles (biased domain), [nTargets]
 };
+
+// One target column of the scan: S = the lane's DP column (R packed registers), M / M2 the running maxima.  word holds the column's
+// residue code in byte b & 3, b = the column's index in its chunk (a constant wherever the call is unrolled).  fold says what an odd R does
+// with its last register, which has no partner in its own column: kFoldAlone folds it with itself, kFoldKeep sets it aside in `kept` (it
+// is dead after the next hand-off anyway), kFoldBoth folds it together with the one kept by the column before -- one max3 per two columns.
+// TILED: bi / bo = the chunk's border words in and out, carryPrev = the border value of the column before the chunk.
+enum { kFoldAlone = 0, kFoldKeep = 1, kFoldBoth = 2 };
+template <int R, bool TILED, bool PAIRED, bool ROLLED>
+__device__ __forceinline__ void gaplessColumn(uint32_t (&S)[R], uint32_t &M, uint32_t &M2, uint32_t &kept, const uint32_t word, const int b, const int fold,
+                                              const uint32_t laneOff, const uint32_t sel, const int g, const uint32_t carryPrev, const uint32_t (&bi)[8], uint32_t (&bo)[8]) {
+    constexpr int CHB = gaplessChunkBytes();
+    constexpr int NCH = gaplessChunks(R);         // ds_read_b128 per column; the last one may carry unused registers
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    // LDS row address, bytes {0, 0, code, laneOff}: S0 = residue word (selector bytes 4..7), S1 = laneOff
+    const uint32_t addr = __builtin_amdgcn_perm(word, laneOff, 0x0c0c0000u | ((4u + (b & 3)) << 8));
+    const unsigned char __attribute__((address_space(3))) *rowp =
+        (const unsigned char __attribute__((address_space(3))) *) (uintptr_t) addr;
+    uint32_t P[4 * NCH];
+    const auto readChunk = [&](const unsigned char __attribute__((address_space(3))) *row, const int k) __attribute__((always_inline)) {
+        const u32x4 v = *(const u32x4 __attribute__((address_space(3))) *) (row + k * CHB);
+        P[4 * k + 0] = v.x; P[4 * k + 1] = v.y; P[4 * k + 2] = v.z; P[4 * k + 3] = v.w;
+        // R % 4 == 1: only v.x of the last chunk feeds the recurrence and the compiler narrows the access to a
+        // ds_read_b32 -- whose 64 lanes are serviced together, so the four targets of a copy collide on one bank
+        // (SQ_LDS_BANK_CONFLICT = 15-20 % of the LDS cycles for R = 17, 21, 25, 29, zero for every other R:
+        // profiles/r02_a_pmc_*).  Keeping the unused words alive keeps the conflict-free 128-bit form.
+        if constexpr (R % 4 == 1) { if (k == NCH - 1) asm volatile("" :: "v"(v.y), "v"(v.z), "v"(v.w)); }
+    };
+    // Source order of the reads.  Unrolled, 4-wave workgroups (R <= 36): all reads of the column first; the compiler overlaps them with the
+    // column before.  Everywhere else they go from the top chunk down, each ahead of the adds of the chunk above it:
+    //  * 8-wave workgroups (R > 36) fit a CU twice only below 128 VGPRs, and reads-first the schedule the compiler finds swings between 87 and
+    //    139 registers from one R to the next (three classes above 128); in this order every class stays below 128;
+    //  * a column on its own (ROLLED: the loop over a stripe's last columns) has no neighbour to overlap with, the compiler would issue all
+    //    reads ahead of the first add -- R profile registers beside the R of S, more than any point of the unrolled loop needs -- so there an
+    //    empty asm also ties the row address to the sums just made: at most two chunks are in flight.
+    constexpr bool readsFirst = !ROLLED && R <= 36;
+    if constexpr (readsFirst) {
+#pragma unroll
+        for (int k = 0; k < NCH; k++) readChunk(rowp, k);
+    }
+    // diagonal hand-off
+    uint32_t prev = __builtin_amdgcn_mov_dpp(S[R - 1], 0x111 /*row_shr:1*/, 0xf, 0xf, true);
+    if constexpr (TILED) {
+        // first lane: the diagonal enters from the previous row tile, column b - 1
+        const uint32_t fromTile = (b == 0) ? carryPrev : ((b & 1) ? (bi[(b - 1) >> 1] & 0xffffu) : (bi[(b - 1) >> 1] >> 16));
+        prev = (g == 0) ? (fromTile << 16) : prev;
+    }
+    const uint32_t in = __builtin_amdgcn_perm(prev, S[R - 1], sel);
+    if constexpr (readsFirst) {
+#pragma unroll
+        for (int r = R - 1; r >= 1; r--) S[r] = pk_addc_f16(S[r - 1], P[r]);
+    } else {
+        uint32_t row = addr;
+        readChunk((const unsigned char __attribute__((address_space(3))) *) (uintptr_t) row, NCH - 1);
+#pragma unroll
+        for (int k = NCH - 1; k >= 0; k--) {
+            if (k > 0) readChunk((const unsigned char __attribute__((address_space(3))) *) (uintptr_t) row, k - 1);
+#pragma unroll
+            for (int r = (4 * k + 3 < R ? 4 * k + 3 : R - 1); r >= 4 * k && r >= 1; r--) S[r] = pk_addc_f16(S[r - 1], P[r]);
+            if constexpr (ROLLED) { if (k > 1) asm volatile("" : "+v"(row), "+v"(S[4 * k])); }
+        }
+    }
+    S[0] = pk_addc_f16(in, P[0]);
+#pragma unroll
+    for (int r = 0; r + 3 < R; r += 4) {
+        M = pk_max3_f16(M, S[r], S[r + 1]);
+        M2 = pk_max3_f16(M2, S[r + 2], S[r + 3]);
+    }
+    if constexpr (R % 4 == 2) M = pk_max3_f16(M, S[R - 2], S[R - 1]);
+    if constexpr (R % 4 == 3) M = pk_max3_f16(M, S[R - 3], S[R - 2]);
+    if constexpr (R % 2 == 1) {
+        uint32_t &Mo = (R % 4 == 1) ? M : M2;
+        if (fold == kFoldAlone) Mo = pk_max3_f16(Mo, S[R - 1], S[R - 1]);
+        else if (fold == kFoldKeep) kept = S[R - 1];
+        else Mo = pk_max3_f16(Mo, kept, S[R - 1]);
+    }
+    if constexpr (TILED) {
+        // last lane: its bottom row (high half of the last register) is the next tile's input
+        const uint32_t v = S[R - 1] >> 16;
+        bo[b >> 1] |= (b & 1) ? (v << 16) : v;
+        // Without an ordering point per column the compiler hoists the LDS profile reads of all 16 unrolled
+        // columns above the border bookkeeping: 256 VGPRs + 346 spilled (kernel 12x slower).  An empty asm that
+        // ties the border word to the running maximum pins each column's work in place: 92 VGPRs, no scratch.
+        asm volatile("" : "+v"(bo[b >> 1]), "+v"(M), "+v"(M2));
+    }
+}
 
 // PAIRED: two SHORT queries of one 16-row class share the kernel's rows -- query A in lanes 0..3 of every target group (rows
 // 0 .. 8R-1), query B in lanes 4..7 -- so the 3 per-column instructions that do not depend on R are paid once for both: a query of
@@ -184,7 +274,9 @@ __global__ __launch_bounds__(gaplessBlockThreads(R)) void k_gapless(GaplessArgs 
         const uint32_t stripe = item.x;
         const bool split = (item.y >> 31) & 1;
         const uint32_t cBegin = (item.y >> 16) & 0x7fffu, cEnd = item.y & 0xffffu;
-        const uint64_t soff = ((uint64_t) item.w << 32) | item.z;
+        const uint64_t soff = ((uint64_t) (item.w & 0x00ffffffu) << 32) | item.z;       // every record carries the trim in the top byte, whoever reads it
+        // real columns of the stripe's last chunk where they are fewer than 16 (wave-uniform, 0 = every chunk of the item is full)
+        const uint32_t tail = TILED ? 0u : (item.w >> 24) & 15u;
         const uint4 *src = a.scan + soff + j;
         // border arrays use the scan layout at 2 bytes per residue: 32 bytes per (chunk, target)
         const uint4 *bin = TILED ? (const uint4 *) a.borderIn + (soff + j) * 2 : nullptr;
@@ -196,8 +288,10 @@ __global__ __launch_bounds__(gaplessBlockThreads(R)) void k_gapless(GaplessArgs 
 #pragma unroll
         for (int r = 0; r < R; r++) S[r] = 0;
 
+        uint32_t kept = 0;                                // odd R: the last register of an even column, see gaplessColumn
         uint4 nxt = src[(size_t) cBegin * 8];
-        for (uint32_t c = cBegin; c < cEnd; c++) {
+        const uint32_t cFull = tail ? cEnd - 1 : cEnd;    // chunks that run all 16 columns
+        for (uint32_t c = cBegin; c < cFull; c++) {
             const uint4 cur = nxt;
             if (c + 1 < cEnd) nxt = src[(size_t) (c + 1) * 8];
             const uint32_t words[4] = {cur.x, cur.y, cur.z, cur.w};
@@ -214,56 +308,27 @@ __global__ __launch_bounds__(gaplessBlockThreads(R)) void k_gapless(GaplessArgs 
                 for (int k = 0; k < 8; k++) bo[k] = 0;
             }
 #pragma unroll
-            for (int b = 0; b < 16; b++) {
-                // LDS row address, bytes {0, 0, code, laneOff}: S0 = residue word (selector bytes 4..7), S1 = laneOff
-                const uint32_t addr = __builtin_amdgcn_perm(words[b >> 2], laneOff, 0x0c0c0000u | ((4u + (b & 3)) << 8));
-                const unsigned char __attribute__((address_space(3))) *rowp =
-                    (const unsigned char __attribute__((address_space(3))) *) (uintptr_t) addr;
-                uint32_t P[4 * NCH];
-#pragma unroll
-                for (int k = 0; k < NCH; k++) {
-                    const u32x4 v = *(const u32x4 __attribute__((address_space(3))) *) (rowp + k * CHB);
-                    P[4 * k + 0] = v.x; P[4 * k + 1] = v.y; P[4 * k + 2] = v.z; P[4 * k + 3] = v.w;
-                    // R % 4 == 1: only v.x of the last chunk feeds the recurrence and the compiler narrows the access to a
-                    // ds_read_b32 -- whose 64 lanes are serviced together, so the four targets of a copy collide on one bank
-                    // (SQ_LDS_BANK_CONFLICT = 15-20 % of the LDS cycles for R = 17, 21, 25, 29, zero for every other R:
-                    // profiles/r02_a_pmc_*).  Keeping the unused words alive keeps the conflict-free 128-bit form.
-                    if constexpr (R % 4 == 1) { if (k == NCH - 1) asm volatile("" :: "v"(v.y), "v"(v.z), "v"(v.w)); }
-                }
-                // diagonal hand-off
-                uint32_t prev = __builtin_amdgcn_mov_dpp(S[R - 1], 0x111 /*row_shr:1*/, 0xf, 0xf, true);
-                if constexpr (TILED) {
-                    // first lane: the diagonal enters from the previous row tile, column b - 1
-                    const uint32_t fromTile = (b == 0) ? carryPrevChunk : ((b & 1) ? (bi[(b - 1) >> 1] & 0xffffu) : (bi[(b - 1) >> 1] >> 16));
-                    prev = (g == 0) ? (fromTile << 16) : prev;
-                }
-                const uint32_t in = __builtin_amdgcn_perm(prev, S[R - 1], sel);
-#pragma unroll
-                for (int r = R - 1; r >= 1; r--) S[r] = pk_addc_f16(S[r - 1], P[r]);
-                S[0] = pk_addc_f16(in, P[0]);
-#pragma unroll
-                for (int r = 0; r + 3 < R; r += 4) {
-                    M = pk_max3_f16(M, S[r], S[r + 1]);
-                    M2 = pk_max3_f16(M2, S[r + 2], S[r + 3]);
-                }
-                if constexpr (R % 4 == 1) M = pk_max3_f16(M, S[R - 1], S[R - 1]);
-                if constexpr (R % 4 == 2) M = pk_max3_f16(M, S[R - 2], S[R - 1]);
-                if constexpr (R % 4 == 3) { M = pk_max3_f16(M, S[R - 3], S[R - 2]); M2 = pk_max3_f16(M2, S[R - 1], S[R - 1]); }
-                if constexpr (TILED) {
-                    // last lane: its bottom row (high half of the last register) is the next tile's input
-                    const uint32_t v = S[R - 1] >> 16;
-                    bo[b >> 1] |= (b & 1) ? (v << 16) : v;
-                    // Without an ordering point per column the compiler hoists the LDS profile reads of all 16 unrolled
-                    // columns above the border bookkeeping: 256 VGPRs + 346 spilled (kernel 12x slower).  An empty asm that
-                    // ties the border word to the running maximum pins each column's work in place: 92 VGPRs, no scratch.
-                    asm volatile("" : "+v"(bo[b >> 1]), "+v"(M), "+v"(M2));
-                }
-            }
+            for (int b = 0; b < 16; b++)
+                gaplessColumn<R, TILED, PAIRED, false>(S, M, M2, kept, words[b >> 2], b, TILED ? kFoldAlone : (b & 1) ? kFoldBoth : kFoldKeep, laneOff, sel, g, carryPrevChunk, bi, bo);
             if constexpr (TILED) {
                 carryPrevChunk = bi[7] >> 16;
                 if (!a.lastTile && g == 7) {
                     bout[(size_t) c * 16] = make_uint4(bo[0], bo[1], bo[2], bo[3]);
                     bout[(size_t) c * 16 + 1] = make_uint4(bo[4], bo[5], bo[6], bo[7]);
+                }
+            }
+        }
+        if constexpr (!TILED) {
+            // The stripe's last chunk (already loaded: nxt) holds `tail` real columns; the rest is the dead code, whose cells are zero and
+            // feed nothing.  The same column body once more, in a loop with a scalar trip count: the codes move down through the four
+            // words, so that every round finds its column in the low byte of the first.
+            if (tail) {
+                uint32_t w0 = nxt.x, w1 = nxt.y, w2 = nxt.z, w3 = nxt.w;
+                uint32_t none[8];
+                for (uint32_t t = 0; t < tail; t++) {
+                    gaplessColumn<R, TILED, PAIRED, true>(S, M, M2, kept, w0, 0, kFoldAlone, laneOff, sel, g, 0u, none, none);
+                    w0 = __builtin_amdgcn_alignbit(w1, w0, 8); w1 = __builtin_amdgcn_alignbit(w2, w1, 8);
+                    w2 = __builtin_amdgcn_alignbit(w3, w2, 8); w3 >>= 8;
                 }
             }
         }

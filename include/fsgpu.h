@@ -145,6 +145,12 @@ int fsgpu_gapless_scores(fsgpu_ctx *ctx, uint8_t *scores_out);
  * written).  Exported so that the policy can be tested without a GPU. */
 int64_t fsgpu_gapless_plan_items(const uint32_t *stripeLen, uint32_t nStripes, int overlap, double waves, uint64_t *items,
                                  uint64_t capacity, uint32_t *cap);
+/* Host-only: the 16-byte device records the scan makes of planned items.  stripeCols[s] = real columns of stripe s (its longest
+ * target), stripeLen[s] = ceil(stripeCols[s] / 16).  records[4 i ..] = {stripe, the item's low word, stripe offset in 16-byte units
+ * low, trim << 24 | offset high}: trim = stripeCols - 16 * (stripeLen - 1) (1..16) for the item that ends with its stripe's last
+ * chunk, 0 for every other.  Returns nItems, or -1 for arguments that do not fit each other. */
+int64_t fsgpu_gapless_item_records(const uint64_t *items, uint64_t nItems, const uint32_t *stripeLen, const uint32_t *stripeCols,
+                                   uint32_t nStripes, uint32_t *records);
 int fsgpu_gapless_launch(fsgpu_ctx *ctx, const int8_t *pssm, int L, int scoreCap, int minScore,
                          int64_t identityId, int maxRes);
 int fsgpu_gapless_finish(fsgpu_ctx *ctx, fsgpu_hit *out, int *nout);
