@@ -146,6 +146,7 @@ def lib():
         "fsgpu_sw3_last_plan": (None, [vp, vp]),
         "fsgpu_kmer_index_build": (i32, [vp, vp, vp]),
         "fsgpu_kmer_index_entries": (u64, [vp]),
+        "fsgpu_kmer_index_entry_bytes": (i32, [vp]),
         "fsgpu_kmer_search": (i32, [vp, vp, vp, i32, vp, vp, vp, vp]),
         "fsgpu_kmer_index_copy": (i32, [vp, vp, vp, vp]),
         "fsgpu_kmer_row_copy": (i32, [vp, i32, vp, vp]),
@@ -218,7 +219,7 @@ def exported_symbols():
             "fsgpu_db_adopt_device", "fsgpu_db_size", "fsgpu_db_residues", "fsgpu_gapless_scan", "fsgpu_gapless_scores",
             "fsgpu_gapless_launch", "fsgpu_gapless_finish", "fsgpu_sw_batch", "fsgpu_sw_multi", "fsgpu_sw_multi_dir", "fsgpu_sw_multi_dir_c", "fsgpu_sw_multi_c", "fsgpu_sw_launch", "fsgpu_sw_finish",
             "fsgpu_db_broadcast", "fsgpu_rccl_selfcheck", "fsgpu_device_count", "fsgpu_live_devices", "fsgpu_gapless_plan_items", "fsgpu_gapless_item_records", "fsgpu_block_backtrace", "fsgpu_block_backtrace_footprint",
-            "fsgpu_lddt_batch", "fsgpu_tm_batch", "fsgpu_last_kernel_ms", "fsgpu_sw_last_passes", "fsgpu_sw3_last_plan", "fsgpu_kmer_index_build", "fsgpu_kmer_index_entries", "fsgpu_kmer_search",
+            "fsgpu_lddt_batch", "fsgpu_tm_batch", "fsgpu_last_kernel_ms", "fsgpu_sw_last_passes", "fsgpu_sw3_last_plan", "fsgpu_kmer_index_build", "fsgpu_kmer_index_entries", "fsgpu_kmer_index_entry_bytes", "fsgpu_kmer_search",
             "fsgpu_kmer_index_copy", "fsgpu_kmer_row_copy", "fsgpu_kmer_last_counts", "fsgpu_kmer_last_segments", "fsgpu_kmer_plan_coarse", "fsgpu_kmer_batch_hint",
             "fsgpu_diag_rescore", "fsgpu_sw_batch_seqs"]
 
@@ -420,6 +421,11 @@ class Context:
     @property
     def kmer_index_entries(self):
         return lib().fsgpu_kmer_index_entries(self.h)
+
+    @property
+    def kmer_index_entry_bytes(self):
+        """4: an index entry is seqId << posBits | position in 32 bits; 8: seqId << 16 | position in 64 (0 before the index is built)"""
+        return lib().fsgpu_kmer_index_entry_bytes(self.h)
 
     def kmer_index_copy(self, nbytes_db):
         off = np.zeros(64000001, np.uint32)

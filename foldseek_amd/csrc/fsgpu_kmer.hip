@@ -177,6 +177,7 @@ static int bitsFor(uint64_t n) { int b = 1; while (b < 32 && (1ull << b) < n) b+
 extern "C" {
 
 uint64_t fsgpu_kmer_index_entries(const fsgpu_ctx *ctx) { return ctx && ctx->kidx ? ctx->kidx->nEntries : 0; }
+int fsgpu_kmer_index_entry_bytes(const fsgpu_ctx *ctx) { return ctx && ctx->kidx ? (ctx->kidx->posBits ? 4 : 8) : 0; }
 
 int fsgpu_kmer_index_build(fsgpu_ctx *ctx, const fsgpu_kmer_index_params *p, const int16_t *kmerSub) {
     if (!ctx || !p || !kmerSub) return FSGPU_E_ARG;
@@ -660,7 +661,8 @@ static int kmerBatch(fsgpu_ctx *ctx, const fsgpu_kmer_search_params &sp, const f
         if (waveForm >= 0 ? waveForm != 0 : ctx->kmerKPerPos < 2048)
         {
             // few similar k-mers per position: the small LDS form (more waves per SIMD); FSGPU_KMER_WAVE_SMALL = 0 / 1 forces a form (A/B)
-            static const int smallEnv = [] { const char *e = getenv("FSGPU_KMER_WAVE_SMALL"); return e && *e ? atoi(e) : -1; }();
+            const char *se = getenv("FSGPU_KMER_WAVE_SMALL");
+            const int smallEnv = se && *se ? atoi(se) : -1;
             const bool small = smallEnv >= 0 ? smallEnv != 0 : ctx->kmerKPerPos < 128;
             if (small)
                 hipLaunchKernelGGL((k_kmer_lists_w<128, 64>), dim3((unsigned) ((nPos + 3) / 4)), dim3(256), 0, st, (const KmerQ *) S.qs.p, (const uint16_t *) S.posQuery.p,
@@ -872,7 +874,8 @@ static int kmerBatch(fsgpu_ctx *ctx, const fsgpu_kmer_search_params &sp, const f
             for (int q = 0; q < nq; q++) maxL = std::max(maxL, queries[q].L);
             const int ldsBytes = std::min(maxL * 21, 60 * 1024);
             // eight lanes per candidate (k_kmer_score8) unless FSGPU_KMER_SCORE8=0 asks for the one-lane-per-candidate form (A/B runs)
-            static const bool score8 = [] { const char *e = getenv("FSGPU_KMER_SCORE8"); return !(e && atoi(e) == 0); }();
+            const char *s8 = getenv("FSGPU_KMER_SCORE8");
+            const bool score8 = !(s8 && atoi(s8) == 0);
             if (score8)
                 hipLaunchKernelGGL(k_kmer_score8, dim3(gridFor(nCand, 32)), dim3(256), (size_t) ldsBytes, st, (const uint32_t *) S.ckeys.p, (const uint64_t *) S.cvals.p,
                                    (const uint32_t *) S.nCand.p, tbits, (const KmerQ *) S.qs.p, (const int8_t *) S.profiles.p, ix.masked, db.dOffsets, db.dLengths,
@@ -885,7 +888,8 @@ static int kmerBatch(fsgpu_ctx *ctx, const fsgpu_kmer_search_params &sp, const f
             RPCHK(hipEventRecord(S.ev[6], st));
             // ---- stage 4: per-target replay ----------------------------------------------------------------------
             // FSGPU_KMER_WALK_FF=0: every round of every target is walked (A/B runs; the truncation replay below always uses that form)
-            static const bool walkFF = [] { const char *e = getenv("FSGPU_KMER_WALK_FF"); return !(e && atoi(e) == 0); }();
+            const char *wf = getenv("FSGPU_KMER_WALK_FF");
+            const bool walkFF = !(wf && atoi(wf) == 0);
             if (walkFF)
                 hipLaunchKernelGGL(k_kmer_walk<true>, dim3(gridFor(nCand, 128)), dim3(128), 0, st, (const uint32_t *) S.ckeys.p, (const uint64_t *) S.cvals.p,
                                    (const uint8_t *) S.kept.p, (const int32_t *) S.score.p, (const uint32_t *) S.nCand.p, tbits, (const KmerChunks *) S.chunks.p,

@@ -348,6 +348,8 @@ typedef struct {
  * bits and the position bits of the database fit 32 together, 8 bytes otherwise. */
 int fsgpu_kmer_index_build(fsgpu_ctx *ctx, const fsgpu_kmer_index_params *p, const int16_t *kmerSubMat21x21);
 uint64_t fsgpu_kmer_index_entries(const fsgpu_ctx *ctx);
+/* Bytes of one index entry of the resident index: 4 or 8 (see above; FSGPU_KMER_ENTRY64=1 at build time keeps the 8-byte form); 0 before an index is built. */
+int fsgpu_kmer_index_entry_bytes(const fsgpu_ctx *ctx);
 /* Inspection (tests): copy the offset table (64e6+1 uint32), the entries (seqId << 16 | position) and/or the masked
  * sequence lookup (padded DB layout) to host memory; any pointer may be NULL.  The table is kept in the DEVICE k-mer
  * order: index = first3mer * 8000 + last3mer (the reference numbers k-mers first3mer + 8000 * last3mer).  Row `row` of the extended 3-mer matrix. */

@@ -60,6 +60,7 @@ typedef struct {
     uint8_t *lookup;
     int64_t *lookOff;          /* n + 1 */
     int pattern[32], patternSize, kpos[16];
+    int64_t lastRefills;       /* databaseHits refills of the last fko_query (stats[2] only says whether there were any) */
 } fko;
 
 /* ---- spaced patterns (M/src/commons/Sequence.h:18-60); only the sizes the structure prefilter can pick ---- */
@@ -332,6 +333,7 @@ void *fko_create(const fko_params *p, const int16_t *kmerSub21, const double *pb
 void fko_set_params(void *hv, const fko_params *p) { ((fko *) hv)->p = *p; }
 
 /* ---- accessors for piecewise pinning -------------------------------------------------------------------- */
+int64_t fko_last_refills(void *hv) { return ((fko *) hv)->lastRefills; }
 int64_t fko_index_entries(void *hv) { return (int64_t) ((fko *) hv)->nEntries; }
 int64_t fko_index_list(void *hv, int64_t kmer, uint32_t *seqId, uint16_t *pos, int64_t cap) {
     fko *h = (fko *) hv;
@@ -647,6 +649,7 @@ int fko_query(void *hv, const uint8_t *qcodes, int L, int64_t identity, fko_hit 
     /* ---- QueryMatcher::match -------------------------------------------------------------------------- */
     size_t kmerListLen = 0, numMatches = 0, overflowNumMatches = 0, overflowHitCount = 0, nh = 0, hitCount = 0;
     int overflow = 0, aborted = 0, unsupported = 0;
+    h->lastRefills = 0;
     uint8_t kmer[16];
     for (int cur = 0; !aborted; cur++) {
         int r = kmer_at(h, q, L, cur, kmer);
@@ -664,6 +667,7 @@ int fko_query(void *hv, const uint8_t *qcodes, int L, int64_t identity, fko_hit 
             const uint64_t o0 = h->offsets[list[kp]], sz = h->offsets[list[kp] + 1] - o0;
             if (nh + sz >= maxDbMatches) {
                 overflow = 1;
+                h->lastRefills++;
                 const size_t hc = p->noDiagScore ? cfo_find_duplicates_total(&cfo, hits, nh, found + overflowHitCount, foundSize - overflowHitCount)
                                                  : cfo_find_duplicates(&cfo, hits, nh, found + overflowHitCount, foundSize - overflowHitCount);
                 if (overflowHitCount != 0 && p->noDiagScore) {

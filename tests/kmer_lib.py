@@ -5,6 +5,7 @@ import os
 import numpy as np
 
 import oracle_lib
+from foldseek_amd import synth
 
 ALPHABET = "ACDEFGHIKLMNPQRSTVWYX"
 _A = np.frombuffer(ALPHABET.encode(), np.uint8)
@@ -76,7 +77,7 @@ def load_ref():
 def load_ora():
     L = oracle_lib.load_oracle()
     L.fko_create.restype = C.c_void_p
-    for f in ("fko_index_entries", "fko_index_list", "fko_index_offsets", "fko_kmer_list", "fko_scorematrix_row"):
+    for f in ("fko_last_refills", "fko_index_entries", "fko_index_list", "fko_index_offsets", "fko_kmer_list", "fko_scorematrix_row"):
         getattr(L, f).restype = C.c_int64
     return L
 
@@ -168,6 +169,26 @@ class OraKpf:
         pb = np.ascontiguousarray(pback, np.float64)
         self.h = C.c_void_p(L.fko_create(C.byref(self.p), _vp(ks), _vp(pb), _vp(us), _vp(cat), _vp(off), _vp(lens), C.c_int64(self.n)))
 
+    @classmethod
+    def from_padded(cls, L, kmer_sub, pback, ung_sub, db, **kw):
+        """the same over a padded database (synth.PaddedDB) without per-target Python objects: the oracle reads the targets through the
+        database's own offsets / lengths (mask flags kept, the padding between them is never looked at)"""
+        self = cls.__new__(cls)
+        self.L, self.p = L, default_params(OraParams, **kw)
+        cat = np.ascontiguousarray(db.data3di, np.uint8)
+        off = np.ascontiguousarray(db.offsets, np.int64)
+        lens = np.ascontiguousarray(db.lengths, np.int32)
+        self.n = int(db.n)
+        ks = np.ascontiguousarray(kmer_sub, np.int16); us = np.ascontiguousarray(ung_sub, np.int16)
+        pb = np.ascontiguousarray(pback, np.float64)
+        self.h = C.c_void_p(L.fko_create(C.byref(self.p), _vp(ks), _vp(pb), _vp(us), _vp(cat), _vp(off), _vp(lens), C.c_int64(self.n)))
+        return self
+
+    @property
+    def last_refills(self):
+        """databaseHits refills of the last query() (stats[2] is only the 0/1 flag the device statistics are compared with)"""
+        return int(self.L.fko_last_refills(self.h))
+
     def close(self):
         if self.h:
             self.L.fko_free(self.h)
@@ -226,3 +247,49 @@ class OraKpf:
         s = np.zeros(size, np.int16); ix = np.zeros(size, np.uint32)
         self.L.fko_scorematrix_row(self.h, which, C.c_int64(idx), _vp(s), _vp(ix))
         return s, ix
+
+
+# ---- the wide database of tests/test_kmer_edges_gpu.py and tests/test_kmer_oracle_vs_ref.py ---------------------------------------
+WIDE_N = 300000
+
+
+def wide_world(last_len):
+    """300 000 targets of 8 .. 24 residues (19 id bits) whose LAST id is replaced by one target of `last_len` residues: 8191 -> 13 position
+    bits, id and position fill the 32 bits of a 4-byte index entry; 8192 -> 14 bits, the index takes 8-byte entries.  Six queries of
+    40 .. 400 residues with 400 planted homologs each; the long target is i.i.d. letters around a 60-residue piece of query 4 at
+    position 5000 (a hit with id n - 1 on a negative diagonal).  The two variants share every other byte.  -> (db, q3)"""
+    q3, qa = synth.make_queries(6, seed=44, mean_len=200, lo=40, hi=400)          # 400, 214, 294, 127, 221, 295 residues
+    db = synth.make_db_fast(WIDE_N, (q3, qa), seed=42, homologs_per_query=400, mask_frac=0.01, mean_len=16.0, lo=8, hi=24)
+    rng = np.random.default_rng(43)
+    long3 = synth._draw(rng, 8192, synth.BACK_3DI)[:last_len]
+    longa = synth._draw(rng, 8192, synth.BACK_AA)[:last_len]
+    piece = slice(len(q3[4]) - 60, len(q3[4]))
+    long3[5000:5060] = q3[4][piece]; longa[5000:5060] = qa[4][piece]
+    o = int(db.offsets[-2])
+    pad = np.full((last_len + 3) // 4 * 4 - last_len, 20, np.uint8)
+    d3 = np.concatenate([db.data3di[:o], long3, pad]); da = np.concatenate([db.dataaa[:o], longa, pad])
+    offsets = db.offsets.copy(); offsets[-1] = d3.size
+    lengths = db.lengths.copy(); lengths[-1] = last_len
+    return synth.PaddedDB(d3, da, offsets, lengths), q3
+
+
+def long_query(db, L, first):
+    """L residues out of members of the 3000-target database of test_kmer_gpu.py: the tail of target 2990 from its residue 150 on (hits on the negative
+    diagonal -150), then whole members first, first - 7, ..."""
+    parts = [db.seq(2990)[150:]]
+    have, i = len(parts[0]), first
+    while have < L:
+        parts.append(db.seq(i)); have += len(parts[-1]); i -= 7
+    return np.concatenate(parts)[:L]
+
+
+LONG_QUERIES = ((2925, 2999), (2926, 2998), (6000, 2997), (20000, 2996))          # (residues, first member)
+
+
+def longest_query_world():
+    """the 60 short targets of test_tiny_database_one_key_one_round and a query of 32768 residues tiled from them behind the tail of target 59
+    (cut to 32767: the longest the prefilter takes) -> (db, q3, query)"""
+    q3, qa = synth.make_queries(5, seed=11, mean_len=30, lo=12, hi=40)
+    db = synth.make_db(60, (q3, qa), seed=12, homologs_per_query=3, mean_len=40, lo=12, hi=80)
+    every = np.concatenate([db.seq(i) for i in range(db.n)])
+    return db, q3, np.concatenate([db.seq(59)[20:], np.tile(every, 32768 // len(every) + 1)])[:32768]

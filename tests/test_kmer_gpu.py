@@ -97,8 +97,8 @@ def test_hit_lists(world, kw):
 
 @pytest.mark.parametrize("kw", [dict(), dict(maxResListLen=300, maxDbMatches=5000, foundDiagonalsSize=40000)])
 def test_every_bin_level_gives_the_same_hits(world, kw, monkeypatch):
-    """the hit-stream partition may cut the targets into coarse keys of any granularity (the residue-balanced default, or 1 / 2 / 4 ... blocks of
-    1024 ids per key): the (query, chunk, key) runs change, the hits do not (incl. the databaseHits refill rounds of the second parameter set)"""
+    """the hit-stream partition may cut the targets into coarse keys of any granularity (level 0: about 128 keys of equal residue
+    count, which no batch selects on its own and only FSGPU_KMER_BIN_LEVEL=0 reaches; or 1 / 2 / 4 ... blocks of 1024 ids per key): the (query, chunk, key) runs change, the hits do not (incl. the databaseHits refill rounds of the second parameter set)"""
     o, q3, ctx = world["o"], world["q3"], world["ctx"]
     base = dict(maxResListLen=1000, bins=0, maxDbMatches=0, foundDiagonalsSize=0, compBias=1, minDiagScoreThr=30)
     base.update(kw)

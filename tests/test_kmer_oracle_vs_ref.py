@@ -246,3 +246,99 @@ def test_find_duplicates_cut_short_oracle_equals_the_compiled_reference():
             cut_refilled += differs and st[2] > 0
         o.close()
     assert compared >= 25 and cut >= 15 and cut_refilled >= 5, (compared, cut, cut_refilled)
+
+
+# ---- the shapes tests/test_kmer_edges_gpu.py holds the device to: the oracle is only as good as its pin ------------------------------------
+def _pin(r, o, qs, ident, **kw):
+    """reference and oracle with one parameter set: hit lists and statistics identical -> (lists, reference statistics, the oracle's refill counts)"""
+    base = dict(maxResListLen=1000, bins=0, maxDbMatches=0, foundDiagonalsSize=0, compBias=1, minDiagScoreThr=30)
+    base.update(kw)
+    r.set(**base); o.set(**base)
+    rr, rs, _ = r.run(qs, ident)
+    refills = []
+    for i, q in enumerate(qs):
+        b, st = o.query(q, -1 if ident is None else int(ident[i]))
+        refills.append(o.last_refills)
+        assert b is not None and len(b) == len(rr[i]) and (b == rr[i]).all(), (i, kw, len(b), len(rr[i]))
+        assert np.allclose(st[:3], rs[i][:3]), (i, kw, st, rs[i])
+        assert (refills[-1] > 0) == (rs[i][2] > 0), (i, kw, refills[-1])
+    return rr, rs, refills
+
+
+@pytest.fixture(scope="module")
+def small3000():
+    """the 3000-target database of test_kmer_gpu.py / test_kmer_edges_gpu.py"""
+    R = K.load_ref()
+    if R is None:
+        pytest.skip("oracle/_ref not built")
+    q3, qa = synth.make_queries(6, seed=1)
+    db = synth.make_db(3000, (q3, qa), homologs_per_query=30, mask_frac=0.02)
+    targets = [db.seq(i, "3di", unmask=False) for i in range(db.n)]
+    ksub, pb = H.o_submat("MAT3DI", 8.0, -0.2)
+    usub, _ = H.o_submat("MAT3DI", 2.0, -0.2)
+    r = K.RefKpf(R, targets)
+    o = K.OraKpf(K.load_ora(), ksub, pb, usub, targets)
+    yield dict(r=r, o=o, q3=q3, db=db)
+    r.close(); o.close()
+
+
+def test_long_queries(small3000):
+    """2925 .. 20000 residues (beyond 2925 the device reads the profile from global memory); diagonals on both sides of 0"""
+    r, o, db = small3000["r"], small3000["o"], small3000["db"]
+    qs = [K.long_query(db, L, first) for L, first in K.LONG_QUERIES] + [small3000["q3"][0][:50]]
+    rr, rs, refills = _pin(r, o, qs, None)
+    assert all(len(x) > 0 for x in rr) and all((x["diag"] > 32767).any() for x in rr[:4]) and refills[3] >= 1
+
+
+def test_longest_query():
+    R = K.load_ref()
+    if R is None:
+        pytest.skip("oracle/_ref not built")
+    db, q3, q = K.longest_query_world()
+    targets = [db.seq(i, "3di", unmask=False) for i in range(db.n)]
+    ksub, pb = H.o_submat("MAT3DI", 8.0, -0.2)
+    usub, _ = H.o_submat("MAT3DI", 2.0, -0.2)
+    r = K.RefKpf(R, targets, kmerThr=100)
+    o = K.OraKpf(K.load_ora(), ksub, pb, usub, targets, kmerThr=100)
+    rr, _, _ = _pin(r, o, [q[:32767]] + list(q3), None, kmerThr=100, maxResListLen=50, minDiagScoreThr=15)
+    assert len(rr[0]) == 50 and (rr[0]["diag"] > 32767).any()
+    r.close(); o.close()
+
+
+def test_more_than_255_refills(small3000):
+    """the reference has no limit on databaseHits refills (the device replays 255): 9, 255, 256 and several hundred of them"""
+    r, o, q3 = small3000["r"], small3000["o"], small3000["q3"]
+    qs = [q3[0], q3[1][:60], q3[1], q3[2][:40], q3[4][:100]]
+    ident = np.array([-1, -1, -1, 5, -1], np.int64)
+    for m, want in ((4674, 9), (166, 255), (165, 256), (100, None)):
+        rr, rs, refills = _pin(r, o, qs, ident, maxDbMatches=m, maxResListLen=300)
+        assert (refills[0] == want if want else refills[0] > 400) and len(rr[0]) > 0, (m, refills)
+
+
+def test_one_list_fills_database_hits(small3000):
+    """a single index list of maxDbMatches entries or more: match() gives up (QueryMatcher.cpp:330-332) -- no hits but the identity, statistics cut short"""
+    r, o, q3 = small3000["r"], small3000["o"], small3000["q3"]
+    qs = [q3[0], q3[0], q3[0][:11], q3[3][5:18]]
+    ident = np.array([-1, 7, -1, -1], np.int64)
+    _, whole, _ = _pin(r, o, qs, ident, maxResListLen=100)
+    for m in (4, 6, 8):
+        rr, rs, refills = _pin(r, o, qs, ident, maxDbMatches=m, maxResListLen=100)
+        assert len(rr[0]) == 0 and rs[0][1] < whole[0][1] and len(rr[1]) == 1 and rr[1][0]["id"] == 7 and len(rr[3]) == 0, (m, rs)
+        assert len(rr[2]) > 0 and rs[2][1] == whole[2][1], (m, rs)                          # and a query that does not give up
+
+
+@pytest.mark.parametrize("last_len", [8191, 8192])
+def test_wide_database(last_len):
+    """300 000 short targets and one of 8191 / 8192 residues as the last id (test_kmer_edges_gpu.py: index entries of 32 used bits / of 8 bytes)"""
+    R = K.load_ref()
+    if R is None:
+        pytest.skip("oracle/_ref not built")
+    db, q3 = K.wide_world(last_len)
+    ksub, pb = H.o_submat("MAT3DI", 8.0, -0.2)
+    usub, _ = H.o_submat("MAT3DI", 2.0, -0.2)
+    r = K.RefKpf.from_padded(R, db)
+    o = K.OraKpf.from_padded(K.load_ora(), ksub, pb, usub, db)
+    assert (r.offsets() == o.offsets()).all()
+    rr, _, _ = _pin(r, o, [q3[0], q3[2], q3[4]], np.array([-1, db.n - 1, -1], np.int64), minDiagScoreThr=15)
+    assert db.n - 1 in rr[2]["id"] and rr[1][0]["id"] == db.n - 1
+    r.close(); o.close()
