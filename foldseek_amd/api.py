@@ -53,6 +53,7 @@ DIAG_PAIR_DT = np.dtype([("query", np.uint32), ("target", np.uint32), ("diagonal
 DIAG_RES_DT = np.dtype([("score", np.int32), ("startPos", np.int32), ("endPos", np.int32), ("revScore", np.int32), ("diagonalLen", np.int32),
                         ("identicalAA", np.int32), ("status", np.int32), ("reserved", np.int32)])   # fsgpu_diag_res
 FSGPU_DIAG_OK, FSGPU_DIAG_NO_OVERLAP, FSGPU_DIAG_UNDEFINED, FSGPU_DIAG_BAD_ID = 0, 1, 2, 3
+FSGPU_MAX_SEQ_LEN = 65535      # include/fsgpu.h: the longest query or target an entry takes
 
 
 class BtQuery(C.Structure):
@@ -142,6 +143,7 @@ def lib():
         "fsgpu_sw_launch": (i32, [vp, vp, vp, vp, vp, i32, vp, i32, i32, i32]),
         "fsgpu_sw_finish": (i32, [vp, vp, vp]),
         "fsgpu_last_kernel_ms": (f64, [vp, i32]),
+        "fsgpu_history_counters": (None, [vp, vp]),
         "fsgpu_sw_last_passes": (None, [vp, vp]),
         "fsgpu_sw3_last_plan": (None, [vp, vp]),
         "fsgpu_kmer_index_build": (i32, [vp, vp, vp]),
@@ -219,7 +221,7 @@ def exported_symbols():
             "fsgpu_db_adopt_device", "fsgpu_db_size", "fsgpu_db_residues", "fsgpu_gapless_scan", "fsgpu_gapless_scores",
             "fsgpu_gapless_launch", "fsgpu_gapless_finish", "fsgpu_sw_batch", "fsgpu_sw_multi", "fsgpu_sw_multi_dir", "fsgpu_sw_multi_dir_c", "fsgpu_sw_multi_c", "fsgpu_sw_launch", "fsgpu_sw_finish",
             "fsgpu_db_broadcast", "fsgpu_rccl_selfcheck", "fsgpu_device_count", "fsgpu_live_devices", "fsgpu_gapless_plan_items", "fsgpu_gapless_item_records", "fsgpu_block_backtrace", "fsgpu_block_backtrace_footprint",
-            "fsgpu_lddt_batch", "fsgpu_tm_batch", "fsgpu_last_kernel_ms", "fsgpu_sw_last_passes", "fsgpu_sw3_last_plan", "fsgpu_kmer_index_build", "fsgpu_kmer_index_entries", "fsgpu_kmer_index_entry_bytes", "fsgpu_kmer_search",
+            "fsgpu_lddt_batch", "fsgpu_tm_batch", "fsgpu_last_kernel_ms", "fsgpu_history_counters", "fsgpu_sw_last_passes", "fsgpu_sw3_last_plan", "fsgpu_kmer_index_build", "fsgpu_kmer_index_entries", "fsgpu_kmer_index_entry_bytes", "fsgpu_kmer_search",
             "fsgpu_kmer_index_copy", "fsgpu_kmer_row_copy", "fsgpu_kmer_last_counts", "fsgpu_kmer_last_segments", "fsgpu_kmer_plan_coarse", "fsgpu_kmer_batch_hint",
             "fsgpu_diag_rescore", "fsgpu_sw_batch_seqs"]
 
@@ -772,6 +774,14 @@ class Context:
 
     def kernel_ms(self, which):
         return lib().fsgpu_last_kernel_ms(self.h, which)
+
+    def history_counters(self):
+        """fsgpu_history_counters: the choices this context made from what it ran before"""
+        o = np.zeros(8, np.uint64)
+        lib().fsgpu_history_counters(self.h, _ptr(o))
+        o = [int(v) for v in o]
+        return {"kmer_count_form": o[0], "kmer_list_form": o[1], "kmer_batches": o[2], "kmer_last_batch_queries": o[3],
+                "sw_long_launched": o[4], "sw_long_reused": o[5], "lddt_norm_runs": o[6], "kmer_first_batch_queries": o[7]}
 
     def sw_last_passes(self):
         """[[ms, cells, pairs, DP wave-instructions] forward, [...] reversed] of the last multi-query SW passes (k_sw2 launches only)"""

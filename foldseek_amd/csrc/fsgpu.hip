@@ -78,11 +78,8 @@ void fsgpu_destroy(fsgpu_ctx *ctx) {
     if (ctx->swLong) (void) hipStreamSynchronize(ctx->swLong);
     if (ctx->swHi) (void) hipStreamSynchronize(ctx->swHi);          // the k_sw3 path runs here and on swAux: nothing may be in flight when its buffers go
     for (int i = 0; i < fsgpu_ctx::kSwAux; i++) if (ctx->swAux[i]) (void) hipStreamSynchronize(ctx->swAux[i]);
-    if (ctx->scanDoneEv) {
-        if (ctx->db) { std::lock_guard<std::mutex> g(ctx->db->scanMutex); if (ctx->db->lastScanDone == ctx->scanDoneEv) ctx->db->lastScanDone = nullptr; }
-        (void) hipEventDestroy(ctx->scanDoneEv);
-    }
-    freeDb(ctx);
+    freeDb(ctx);                                                    // leaves the DbStore's chain of scan events before the event goes
+    if (ctx->scanDoneEv) (void) hipEventDestroy(ctx->scanDoneEv);
     if (ctx->kmer) fsgpu_kmer_free_scratch(ctx->kmer);
     DevBuf *bufs[] = {&ctx->gBorder0, &ctx->gBorder1, &ctx->scoreAcc, &ctx->pssm, &ctx->scores, &ctx->chunkHist, &ctx->baseGt, &ctx->baseTie, &ctx->outId, &ctx->outScore,
                       &ctx->img, &ctx->tids, &ctx->res0, &ctx->res1, &ctx->border0, &ctx->border1, &ctx->keys, &ctx->lbuf, &ctx->lres,
@@ -128,6 +125,13 @@ void fsgpu_sw_last_passes(const fsgpu_ctx *ctx, double *out) {
         out[d * 4 + 0] = ms >= 0 ? ms + (float) ctx->swDirExtraMs[d] : ms;
         out[d * 4 + 1] = ctx ? ctx->swDirCells[d] : 0; out[d * 4 + 2] = ctx ? ctx->swDirPairs[d] : 0; out[d * 4 + 3] = ctx ? ctx->swDirWaveSteps[d] : 0;
     }
+}
+
+void fsgpu_history_counters(const fsgpu_ctx *ctx, uint64_t *out8) {
+    for (int i = 0; i < 8; i++) out8[i] = 0;
+    if (!ctx) return;
+    out8[0] = ctx->kmerForm[0]; out8[1] = ctx->kmerForm[1]; out8[2] = ctx->kmerBatches; out8[3] = ctx->kmerLastBatchQueries;
+    out8[4] = ctx->swLongLaunched; out8[5] = ctx->swLongReused; out8[6] = ctx->ldNormRuns; out8[7] = ctx->kmerFirstBatchQueries;
 }
 
 double fsgpu_last_kernel_ms(const fsgpu_ctx *ctx, int which) {

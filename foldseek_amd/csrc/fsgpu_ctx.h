@@ -89,6 +89,9 @@ struct fsgpu_ctx {
     bool kmerDupAttr = false;                      // k_kmer_dup_stream may use more than 60 KB of dynamic LDS on this context's device (its table is one byte per target id of a key)
     int kmerBatchOk = 0;                           // batches that succeeded in a row under the current cap (it is relaxed after four)
     uint64_t kmerCounts[4] = {0, 0, 0, 0};   // last batch: k-mer lists probed, index hits, double-diagonal candidates, elements handed to the host
+    // fsgpu_history_counters: what the last k-mer batch's count pass and list pass ran as (0 nothing, 1 workgroup per position, 2 wave per position), device
+    // batches of the last fsgpu_kmer_search call, queries of its last and of its first batch
+    uint32_t kmerForm[2] = {0, 0}, kmerBatches = 0, kmerLastBatchQueries = 0, kmerFirstBatchQueries = 0;
 
     // gapless scratch
     DevBuf pssm, scores, chunkHist, baseGt, baseTie, outId, outScore, gBorder0, gBorder1, scoreAcc;
@@ -99,6 +102,7 @@ struct fsgpu_ctx {
     PinBuf hOutId, hOutScore;            // pinned
     int pendingMaxRes = 0;
     bool gaplessPending = false;
+    bool scoresValid = false;            // `scores` holds the last single-query scan of the database that is loaded NOW (fsgpu_gapless_scores)
     // multi-query scan (fsgpu_gapless_scan_multi): per-batch arrays, query-major
     DevBuf mqPssm, mqScores, mqQueues, mqRec, mqHist, mqBaseGt, mqBaseTie, mqMeta, mqOutId, mqOutScore, mqIdent;
     PinBuf hMqPssm, hMqRec, hMqMeta, hMqOutId, hMqOutScore, hMqIdent;
@@ -126,7 +130,8 @@ struct fsgpu_ctx {
     DevBuf lbuf, lres;                             // [ids | border bases | tile blocks per level | images], [fwd results | rev results]
     PinBuf hLbuf, hLres;
     struct LongRev { uint64_t hash = 0; std::vector<int32_t> res; };   // reversed-query results of the forward call's k_sw launches (4 int32 per pair, word 0 = not computed)
-    std::vector<LongRev> swLongRev;                // per query of the last dir-0 call
+    std::vector<LongRev> swLongRev;                // per query of the last dir-0 call; dropped with the database (freeDb)
+    uint32_t swLongLaunched = 0, swLongReused = 0; // row-tiled pairs of the last fsgpu_sw_multi_dir call: run on the device / answered from swLongRev
     DevBuf ovAA, ovSS, ovOff, ovLen;               // explicit target sequences of fsgpu_sw_batch_seqs (instead of database entries)
     // fsgpu_sw_multi_dir_c (k_sw3): images built on the device from the compact query data; the images of a forward call are kept for the
     // reversed call over the same queries (s3Sig = hash of what the images depend on)
@@ -145,6 +150,7 @@ struct fsgpu_ctx {
     PinBuf hLdIn, hLdOut;
     hipEvent_t ldEv[3] = {nullptr, nullptr, nullptr};
     double ldMs[2] = {-1, -1};
+    uint64_t ldNormRuns = 0;                    // k_lddt_norm launches of this context (fsgpu_history_counters)
     std::vector<float> ldNormQuery;             // single-query calls (the one-by-one path of structurealign): the coordinates whose norms ldNorm holds, empty = none
     std::vector<uint32_t> ldOrder, ldCounts;
     std::vector<uint64_t> ldColOff;
@@ -230,7 +236,18 @@ inline int ensurePinnedAll(fsgpu_ctx *ctx, std::initializer_list<PinReq> reqs) {
     return FSGPU_OK;
 }
 
-inline void freeDb(fsgpu_ctx *ctx) { ctx->db.reset(); ctx->kidx.reset(); }
+// Lets go of the database (a reload, or the end of the context) and of everything the context kept ABOUT it: the scan results the score getters
+// hand out, the reversed records of row-tiled SW queries, and this context's place in the chain of scan events, which contexts that go on using the
+// DbStore would otherwise wait on after the event is gone.  The caller has synchronised the context's stream.
+inline void freeDb(fsgpu_ctx *ctx) {
+    if (ctx->db && ctx->scanDoneEv) {
+        std::lock_guard<std::mutex> g(ctx->db->scanMutex);
+        if (ctx->db->lastScanDone == ctx->scanDoneEv) ctx->db->lastScanDone = nullptr;
+    }
+    ctx->db.reset(); ctx->kidx.reset();
+    ctx->mqSlot.clear(); ctx->scoresValid = false;
+    ctx->swLongRev.clear();
+}
 
 inline uint64_t hashWords(uint64_t h, const void *p, size_t bytes) {
     const unsigned char *c = (const unsigned char *) p;

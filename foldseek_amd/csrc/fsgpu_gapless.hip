@@ -419,6 +419,7 @@ int fsgpu_gapless_launch(fsgpu_ctx *ctx, const int8_t *pssm, int L, int scoreCap
     HIPCHK(hipMemcpyAsync(ctx->hOutScore.p, ctx->outScore.p, (size_t) K * 4, hipMemcpyDeviceToHost, ctx->stream));
     ctx->pendingMaxRes = (int) K;
     ctx->gaplessPending = true;
+    ctx->scoresValid = true;
     ctx->evValid[0] = true;
     return FSGPU_OK;
 }
@@ -510,7 +511,7 @@ int fsgpu_gapless_last_batch(const fsgpu_ctx *ctx, int *launches, int *queries) 
 
 int fsgpu_gapless_scores(fsgpu_ctx *ctx, uint8_t *scores_out) {
     if (!ctx || !scores_out) return FSGPU_E_ARG;
-    if (!ctx->db || ctx->db->n == 0 || !ctx->scores.p) { ctx->err = "no scan results"; return FSGPU_E_NODB; }
+    if (!ctx->db || ctx->db->n == 0 || !ctx->scores.p || !ctx->scoresValid) { ctx->err = "no scan results for the loaded database"; return FSGPU_E_NODB; }
     HIPCHK(hipStreamSynchronize(ctx->stream));
     HIPCHK(hipMemcpy(scores_out, ctx->scores.p, ctx->db->n, hipMemcpyDeviceToHost));
     return FSGPU_OK;

@@ -630,8 +630,10 @@ static int kmerBatch(fsgpu_ctx *ctx, const fsgpu_kmer_search_params &sp, const f
     // judged by the previous batch of this context, for the list pass by this batch's own count.  FSGPU_KMER_WAVE = 0 / 1 forces a form.
     int waveForm = -1;
     if (const char *e = getenv("FSGPU_KMER_WAVE")) waveForm = atoi(e) != 0;
+    ctx->kmerForm[0] = ctx->kmerForm[1] = 0;
     if (nPos) {
         const bool w = waveForm >= 0 ? waveForm != 0 : (ctx->kmerKPerPos > 0 && ctx->kmerKPerPos < 2048);
+        ctx->kmerForm[0] = w ? 2 : 1;
         if (w)
             hipLaunchKernelGGL(k_kmer_count_w, dim3((unsigned) ((nPos + 3) / 4)), dim3(256), 0, st, (const KmerQ *) S.qs.p, (const uint16_t *) S.posQuery.p,
                                (const uint8_t *) S.seqs.p, (const int16_t *) S.thrs.p, (uint32_t) nPos, ix.pat, ix.s3, (uint32_t *) S.K.p);
@@ -658,7 +660,8 @@ static int kmerBatch(fsgpu_ctx *ctx, const fsgpu_kmer_search_params &sp, const f
     if (nLists) {
         RPCHK(hipEventRecord(S.ev[10], st));
         ctx->kmerKPerPos = (double) nLists / (double) std::max<uint64_t>(nPos, 1);
-        if (waveForm >= 0 ? waveForm != 0 : ctx->kmerKPerPos < 2048)
+        ctx->kmerForm[1] = (waveForm >= 0 ? waveForm != 0 : ctx->kmerKPerPos < 2048) ? 2 : 1;
+        if (ctx->kmerForm[1] == 2)
         {
             // few similar k-mers per position: the small LDS form (more waves per SIMD); FSGPU_KMER_WAVE_SMALL = 0 / 1 forces a form (A/B)
             const char *se = getenv("FSGPU_KMER_WAVE_SMALL");
@@ -1095,6 +1098,7 @@ extern "C" int fsgpu_kmer_search(fsgpu_ctx *ctx, const fsgpu_kmer_search_params 
     const double hitBudget = kKmerHitBudget;
     for (int i = 0; i < 12; i++) ctx->kmerMs[i] = -1;          // < 0: nothing recorded (fsgpu_last_kernel_ms)
     for (int i = 0; i < 4; i++) ctx->kmerCounts[i] = 0;
+    ctx->kmerBatches = 0; ctx->kmerLastBatchQueries = 0; ctx->kmerFirstBatchQueries = 0;
     int q0 = 0;
     while (q0 < nq) {
         int batch = std::min(maxBatch, 32);                   // no history on this context: a batch of 32 shows what a query costs here
@@ -1108,6 +1112,8 @@ extern "C" int fsgpu_kmer_search(fsgpu_ctx *ctx, const fsgpu_kmer_search_params 
         int rc = kmerBatch(ctx, *p, queries + q0, m, out + (size_t) q0 * p->maxResListLen, nout + q0, status + q0, stats ? stats + (size_t) q0 * 4 : nullptr);
         if (rc == 1) { ctx->kmerBatchCap = std::max(1, m / 2); ctx->kmerBatchOk = 0; continue; }            // too many hits / out of memory: redo with half the queries
         if (rc != FSGPU_OK) return rc;
+        if (ctx->kmerBatches++ == 0) ctx->kmerFirstBatchQueries = (uint32_t) m;
+        ctx->kmerLastBatchQueries = (uint32_t) m;
         // one heavy batch does not cap the context for good, but the cap is only relaxed after four batches in a row went through under it: doubling it
         // after every success made every second batch of a run of heavy queries fail, be abandoned after its first stage and be redone
         if (ctx->kmerBatchCap > 0 && ++ctx->kmerBatchOk >= 4) { ctx->kmerBatchCap = 2 * ctx->kmerBatchCap >= maxBatch ? 0 : 2 * ctx->kmerBatchCap; ctx->kmerBatchOk = 0; }

@@ -104,6 +104,7 @@ extern "C" int fsgpu_lddt_batch(fsgpu_ctx *ctx, const fsgpu_lddt_query *queries,
     HIPCHK(hipEventRecord(ctx->ldEv[0], st));
     if (!haveNorm) {
         hipLaunchKernelGGL(k_lddt_norm, dim3((unsigned) ((maxL + kLddtBlock - 1) / kLddtBlock), (unsigned) nq), dim3(kLddtBlock), 0, st, a);
+        ctx->ldNormRuns++;
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipEventRecord(ctx->ldEv[1], st));

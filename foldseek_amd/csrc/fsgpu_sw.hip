@@ -154,8 +154,11 @@ struct SwLongPlan {
     size_t n = 0;
 };
 
-static uint64_t swLongHash(const fsgpu_sw_query &q) {
+// everything the reversed records of one query depend on, the database apart: that one is covered by freeDb, which drops the records
+static uint64_t swLongHash(const fsgpu_sw_query &q, int gapOpen, int gapExtend) {
     uint64_t h = 0xcbf29ce484222325ull ^ (uint64_t) q.L ^ ((uint64_t) q.n << 32);
+    const uint32_t gaps[2] = {(uint32_t) gapOpen, (uint32_t) gapExtend};
+    h = hashWords(h, gaps, sizeof(gaps));
     h = hashWords(h, q.targetIds, (size_t) q.n * 4);
     h = hashWords(h, q.p3Di_rev, (size_t) q.L * kAlphabet * 2);
     if (q.pAA_rev) h = hashWords(h, q.pAA_rev, (size_t) q.L * kAlphabet * 2);
@@ -176,20 +179,21 @@ static int swLongEnqueue(fsgpu_ctx *ctx, const fsgpu_sw_query *q, int nq, const 
         const int ns = sel ? nsel[i] : q[i].n;
         const fsgpu_ctx::LongRev *have = nullptr;
         if (dir == 1 && (size_t) i < ctx->swLongRev.size() && ctx->swLongRev[i].hash != 0 && ctx->swLongRev[i].res.size() == (size_t) q[i].n * 4 &&
-            ctx->swLongRev[i].hash == swLongHash(q[i]))
+            ctx->swLongRev[i].hash == swLongHash(q[i], gapOpen, gapExtend))
             have = &ctx->swLongRev[i];
         lkey.clear();
         for (int k = 0; k < ns; k++) {
             const int j = sel ? sel[i][k] : k;
-            if (have && have->res[(size_t) j * 4 + 3] != 0) { memcpy(&out[base[i] + j], &have->res[(size_t) j * 4], 16); continue; }
+            if (have && have->res[(size_t) j * 4 + 3] != 0) { memcpy(&out[base[i] + j], &have->res[(size_t) j * 4], 16); ctx->swLongReused++; continue; }
             lkey.push_back(((uint64_t) (0xFFFFFF - len[q[i].targetIds[j]]) << 32) | (uint32_t) j);
         }
         std::sort(lkey.begin(), lkey.end());               // longest target first: the waves of a workgroup are of similar length
         for (uint64_t k : lkey) { plan.slotQ.push_back((uint32_t) i); plan.slotJ.push_back((uint32_t) k); }
         plan.n += lkey.size();
-        if (dir == 0) { ctx->swLongRev[i].hash = swLongHash(q[i]); ctx->swLongRev[i].res.assign((size_t) q[i].n * 4, 0); }
+        if (dir == 0) { ctx->swLongRev[i].hash = swLongHash(q[i], gapOpen, gapExtend); ctx->swLongRev[i].res.assign((size_t) q[i].n * 4, 0); }
     }
     qFirst[nq] = plan.n;
+    ctx->swLongLaunched = (uint32_t) plan.n;
     if (plan.n == 0) return FSGPU_OK;
     const size_t n = plan.n;
     const int R = kSwMaxR, rowsPerTile = 64 * R, rowDw = swRowDwords(R);
@@ -438,6 +442,7 @@ int fsgpu_sw_multi_dir(fsgpu_ctx *ctx, const fsgpu_sw_query *q, int nq, int gapO
     int rc;
     if ((rc = swCheckCall(ctx, gapOpen, gapExtend)) != FSGPU_OK) return rc;
     HIPCHK(hipSetDevice(ctx->device));
+    ctx->swLongLaunched = 0; ctx->swLongReused = 0;
     std::vector<size_t> base(nq + 1, 0), sbase(nq + 1, 0);     // offsets into out[] (all pairs) / into the launch (selected pairs)
     bool hasAA = false, anyAA = false, allAA = true;
     for (int i = 0; i < nq; i++) {

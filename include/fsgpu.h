@@ -79,7 +79,13 @@ void fsgpu_destroy(fsgpu_ctx *ctx);
 const char *fsgpu_last_error(const fsgpu_ctx *ctx); /* ctx may be NULL: returns the last creation error */
 /* A second context on the same GPU with its own HIP stream and scratch buffers that SHARES the resident database of
  * `src` (reference counted): lets several host threads keep the device busy, the way the reference runs one aligner
- * object per OpenMP thread over one shared DBReader (F/src/strucclustutils/structurealign.cpp:284-321). */
+ * object per OpenMP thread over one shared DBReader (F/src/strucclustutils/structurealign.cpp:284-321).
+ * What a clone shares, and when: the database AND the k-mer index the source holds AT THE TIME OF THE CALL, both reference counted.  Neither side
+ * sees what the other does afterwards: a clone made before fsgpu_kmer_index_build has no index (fsgpu_kmer_search refuses with FSGPU_E_NODB), a
+ * clone made after it keeps searching that index, by that index's parameters, when the source builds another one or loads another database; the
+ * source may be destroyed while its clones go on.  Everything else is per context, and nothing of it decides an ANSWER: state a context keeps
+ * from call to call (kept LDDT norms, SW images and reversed records, batch sizes of the k-mer search, grow-only workspaces) is either keyed by all
+ * it depends on or dropped when the database goes (fsgpu_db_load, fsgpu_db_adopt_device).  One context serves one host thread at a time. */
 int fsgpu_clone(const fsgpu_ctx *src, fsgpu_ctx **out);
 /* One node, several GPUs, one process: replicates the resident database of `src` into the n contexts dst[] created on
  * OTHER devices, one broadcast per buffer over RCCL (xGMI; librccl is loaded on demand) or peer copies when RCCL is
@@ -132,9 +138,11 @@ int fsgpu_gapless_scan_multi(fsgpu_ctx *ctx, const fsgpu_gapless_query *q, int n
 /* scans / queries of the last fsgpu_gapless_scan_multi: one per launch of the device batch plus one per row-tiled query (> 896 residues, run on
  * its own); fsgpu_last_kernel_ms(ctx, 0) then is the device time of all of them together */
 int fsgpu_gapless_last_batch(const fsgpu_ctx *ctx, int *launches, int *queries);
-/* raw scores of query `queryIndex` of the last fsgpu_gapless_scan_multi call (queries of <= 896 residues); for tests */
+/* raw scores of query `queryIndex` of the last fsgpu_gapless_scan_multi call (queries of <= 896 residues); for tests.  Loading a database forgets
+ * the call: until the next one the getter refuses (FSGPU_E_ARG) and copies nothing. */
 int fsgpu_gapless_scores_multi(fsgpu_ctx *ctx, int queryIndex, uint8_t *scores_out);
-/* Raw per-target scores of the last scan (n bytes, already capped); for tests and statistics. */
+/* Raw per-target scores of the last scan (n bytes, already capped); for tests and statistics.  Refuses (FSGPU_E_NODB) and copies nothing when no
+ * single-query scan has run on the database that is loaded now. */
 int fsgpu_gapless_scores(fsgpu_ctx *ctx, uint8_t *scores_out);
 /* Asynchronous halves of fsgpu_gapless_scan for callers that pipeline several queries / time the device part:
  * _launch enqueues profile upload + kernels on the context stream, _finish waits and post-processes. */
@@ -431,6 +439,12 @@ int fsgpu_kmer_plan_coarse(const int32_t *lengths, uint64_t n, uint32_t blocksPe
  * 16 / 17 the two kernels of the last fsgpu_tm_batch (k_tm_pairs, k_tm_search).
  * Returns < 0 if nothing was recorded. */
 double fsgpu_last_kernel_ms(const fsgpu_ctx *ctx, int which);
+/* Read-only record of the choices a context makes from what it ran before (for tests; nothing reads it back): out8[0] / [1] the form the count pass
+ * / the list pass of the last k-mer device batch ran in (0 not run, 1 one workgroup per query position, 2 one wave per position); [2] device batches
+ * of the last fsgpu_kmer_search call, [3] queries of its last batch; [4] / [5] pairs of row-tiled queries (> 1024 residues) the last
+ * fsgpu_sw_multi_dir call ran on the device / answered from the records its forward call had kept; [6] k_lddt_norm launches of this context since
+ * it was created; [7] queries of the FIRST device batch of the last fsgpu_kmer_search call. */
+void fsgpu_history_counters(const fsgpu_ctx *ctx, uint64_t *out8);
 /* out[2][4], per direction (0 forward, 1 reversed query) of the last fsgpu_sw_multi_dir calls of this context: device ms of that pass's
  * k_sw2 launches (HIP events on the context stream; -1 when the pass did not run), DP cells (query rows x target columns over the
  * single-tile pairs), pairs, and the VALU wave-instructions its waves issue (DP rows + per-step overhead; the issue-rate roofline's unit). */
