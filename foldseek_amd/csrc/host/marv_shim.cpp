@@ -99,6 +99,9 @@ void Marv::setDb(void *dbhandle) {
     if (!db) die("setDb: null database handle");
     if (s->resident != db) {
         const size_t N = s->shards.size();
+        // checked for every shard count: with one shard the caller's buffer goes to the device as it is, and nothing below it looks at the offsets again
+        for (size_t i = 0; i < db->n; i++)
+            if (db->lengths[i] < 0 || db->offsets[i] > db->bytes || (size_t) db->lengths[i] > db->bytes - db->offsets[i]) die("target database: an entry lies outside the data buffer");
         std::vector<uint8_t> packed;              // one shard's entries, contiguous, offsets rebased: a device holds ITS targets only
         for (size_t k = 0; k < N; k++) {
             Shard &sh = s->shards[k];
@@ -120,7 +123,6 @@ void Marv::setDb(void *dbhandle) {
                 const size_t len = extent(i);
                 // a database not written by makepaddedseqdb may end an entry without its padding: never read past the caller's buffer,
                 // the missing bytes are X like the padding would be
-                if (db->offsets[i] > db->bytes || (size_t) db->lengths[i] > db->bytes - db->offsets[i]) die("target database: an entry lies outside the data buffer");
                 const size_t have = std::min<size_t>(len, db->bytes - db->offsets[i]);
                 memcpy(packed.data() + at, db->data + db->offsets[i], have);
                 if (have < len) memset(packed.data() + at + have, 20, len - have);
@@ -158,6 +160,7 @@ Marv::Stats Marv::scan(const char *sequence, size_t sequenceLength, int8_t *pssm
     const size_t L = sequenceLength;
     if (L == 0) return st;
     if (!s->resident) die("scan before setDb");
+    if (s->maxSeqs == 0) die("maxSeqs == 0: a scan that can return no hit is not supported (the device selection needs room for one)");
     // The CPU kernel saturates at 255 - bias with bias = |min(matrix)| + |min(rounded composition bias)|
     // (StripedSmithWaterman.cpp:1375-1406); the caller passes pssm[a][i] = matrix[a][q_i] + round(bias_i) only.
     // (1) A profile that decomposes exactly over a matrix this library carries (3di.out, whose X row is zero, and blosum62.out,
@@ -193,7 +196,8 @@ Marv::Stats Marv::scan(const char *sequence, size_t sequenceLength, int8_t *pssm
         for (size_t i = 0; i < L; i++) {
             const int q = (unsigned char) sequence[i];
             const int cb = pssm[(size_t) X * L + i];
-            if (abs(cb) > 8) die("profile of an unknown substitution matrix whose X row is not a plain composition bias: the CPU path's saturation cap cannot be derived from it");
+            if (abs(cb) > 8) die("profile of a substitution matrix this library does not carry (3di.out, blosum62.out at 2.0 bits) whose X row is not a plain composition bias: "
+                                  "a matrix with a non-zero X row (BLOSUM62 at another scale) is not supported, the CPU path's saturation cap cannot be derived from its profile");
             cbMin = std::min(cbMin, cb);
             for (int a = 0; a < A; a++) {
                 matMin = std::min(matMin, (int) pssm[(size_t) a * L + i] - cb);

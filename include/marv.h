@@ -13,7 +13,9 @@
  *     M/src/alignment/StripedSmithWaterman.cpp:1817-1876); libmarv's half2 kernels do not saturate.
  *   - results are ordered (score desc, id asc), the order hit_t::compareHitsByScoreAndId gives the CPU path.
  *   - AlignmentType GAPLESS only; the other two types (gapped end-position scan) terminate with a message, the way libmarv
- *     terminates on a CUDA error (CUERR).
+ *     terminates on a CUDA error (CUERR).  So do: an alphabet other than 21, maxSeqs == 0 at the first scan, a database entry that
+ *     lies outside the data buffer, and a profile of a matrix other than 3di.out / blosum62.out at 2.0 bits whose X row cannot be a
+ *     rounded composition bias (the saturation cap cannot be derived from it).  tests/test_marv_direct_gpu.py asserts each message.
  *   - like libmarv, one Marv object drives every visible device and shards the TARGETS over them (device k holds targets
  *     k, k + N, ...; per-device top lists merged in the CPU path's order) because its caller hands it one query at a time; the
  *     throughput path shards QUERIES over replicated DBs instead (fsgpu_db_broadcast / fsgpu-modules --gpus).
