@@ -133,6 +133,7 @@ def lib():
         "fsgpu_stream": (vp, [vp]),
         "fsgpu_db_load": (i32, [vp, vp, vp, vp, vp, u64, u64]),
         "fsgpu_db_adopt_device": (i32, [vp, vp, vp, vp, vp, u64, u64]),
+        "fsgpu_db_check_table": (i64, [vp, vp, u64, u64]),
         "fsgpu_db_size": (u64, [vp]),
         "fsgpu_db_residues": (u64, [vp]),
         "fsgpu_gapless_scan": (i32, [vp, vp, i32, i32, i32, i64, i32, vp, C.POINTER(i32)]),
@@ -218,7 +219,7 @@ def lib():
 
 def exported_symbols():
     return ["fsgpu_create", "fsgpu_destroy", "fsgpu_last_error", "fsgpu_device", "fsgpu_stream", "fsgpu_db_load",
-            "fsgpu_db_adopt_device", "fsgpu_db_size", "fsgpu_db_residues", "fsgpu_gapless_scan", "fsgpu_gapless_scores",
+            "fsgpu_db_adopt_device", "fsgpu_db_check_table", "fsgpu_db_size", "fsgpu_db_residues", "fsgpu_gapless_scan", "fsgpu_gapless_scores",
             "fsgpu_gapless_launch", "fsgpu_gapless_finish", "fsgpu_sw_batch", "fsgpu_sw_multi", "fsgpu_sw_multi_dir", "fsgpu_sw_multi_dir_c", "fsgpu_sw_multi_c", "fsgpu_sw_launch", "fsgpu_sw_finish",
             "fsgpu_db_broadcast", "fsgpu_rccl_selfcheck", "fsgpu_device_count", "fsgpu_live_devices", "fsgpu_gapless_plan_items", "fsgpu_gapless_item_records", "fsgpu_block_backtrace", "fsgpu_block_backtrace_footprint",
             "fsgpu_lddt_batch", "fsgpu_tm_batch", "fsgpu_last_kernel_ms", "fsgpu_history_counters", "fsgpu_sw_last_passes", "fsgpu_sw3_last_plan", "fsgpu_kmer_index_build", "fsgpu_kmer_index_entries", "fsgpu_kmer_index_entry_bytes", "fsgpu_kmer_search",
@@ -228,6 +229,15 @@ def exported_symbols():
 
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def db_check_table(offsets, lengths, nbytes):
+    """fsgpu_db_check_table (host only): -1 for a table the load entries take, else the index of the first bad entry (len(lengths) for offsets[n])"""
+    off = np.ascontiguousarray(offsets, np.uint64)
+    ln = np.ascontiguousarray(lengths, np.int32)
+    if len(off) != len(ln) + 1:
+        raise FsgpuError("offsets must have one entry more than lengths")
+    return int(lib().fsgpu_db_check_table(_ptr(off), _ptr(ln), len(ln), int(nbytes)))
 
 
 class Matrix:

@@ -67,7 +67,7 @@ extern "C" int fsgpu_block_backtrace(fsgpu_ctx *ctx, const int8_t *tblAA, const 
     for (int t = 0; t < nt; t++) {
         const fsgpu_bt_task &k = tasks[t];
         if (k.query >= (uint32_t) nq || k.target >= ctx->db->n || k.qEnd < 0 || k.qEnd >= queries[k.query].L || k.dbEnd < 0 || k.dbEnd >= len[k.target]) {
-            ctx->err = "fsgpu_block_backtrace: task out of range"; return FSGPU_E_ARG;
+            ctx->err = "fsgpu_block_backtrace: task out of range (task " + std::to_string(t) + ": ids and an end cell inside the query and the target; a target without residues has none)"; return FSGPU_E_ARG;
         }
         btOff[t] = btBytes;
         btBytes += up16((size_t) k.qEnd + 1 + (size_t) k.dbEnd + 1 + 8);

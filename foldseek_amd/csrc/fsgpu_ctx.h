@@ -53,7 +53,7 @@ struct DbStore {
     // use by gaplessItems() (fsgpu_gapless.hip), shared by all contexts of this DB
     std::vector<uint32_t> hStripeLen;
     std::vector<uint32_t> hStripeCols;   // real columns of every stripe (its longest target); hStripeLen = ceil(this / 16)
-    struct ItemList { uint4 *items = nullptr; uint32_t n = 0; bool split = false, built = false; };
+    struct ItemList { uint4 *items = nullptr; uint32_t n = 0; bool needsClear = false, built = false; };   // needsClear: the plan does not store every target's score byte (see gaplessItems)
     ItemList itemLists[kGaplessMaxRUntiled + 1];
     std::mutex itemMutex;
     // multi-query scans of the contexts sharing this DB run one after the other ON THE DEVICE: a context enqueues its scan

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "fsgpu_ctx.h"
+#include "fs_db_table.h"
 
 // ------------------------------------------------------------------------------------------------------------
 // database re-tiling kernels
@@ -49,12 +50,25 @@ __global__ void k_db_unmask(const uint8_t *raw, uint8_t *out, uint64_t bytes) {
     }
 }
 
+// the table against the buffer before anything reads through it: FSGPU_E_ARG and a message that names the first bad entry
+static int checkTable(fsgpu_ctx *ctx, const char *who, const uint64_t *offsets, const int32_t *lengths, uint64_t n, uint64_t bytes) {
+    const int64_t bad = fsDbCheckTable(offsets, lengths, n, bytes);
+    if (bad < 0) return FSGPU_OK;
+    const char *why = "shares bytes with another entry";
+    if ((uint64_t) bad == n) why = "(offsets[n], the end of the table) lies beyond the data buffer";
+    else if (lengths[bad] < 0 || lengths[bad] > FSGPU_MAX_SEQ_LEN) why = "has a length outside 0 .. FSGPU_MAX_SEQ_LEN";
+    else if (offsets[bad] > bytes || (uint64_t) lengths[bad] > bytes - offsets[bad]) why = "lies outside the data buffer";
+    ctx->err = std::string(who) + ": entry " + std::to_string(bad) + " " + why;
+    return FSGPU_E_ARG;
+}
+
+// hLen: the lengths on the host, already checked (checkTable); dOff / dLen: the same table on the device
 static int buildDb(fsgpu_ctx *ctx, const uint8_t *dRaw3di, const uint8_t *dRawAA, const uint64_t *dOff, const int32_t *dLen,
-                   uint64_t n, uint64_t bytes) {
+                   std::vector<int32_t> &&hLen, uint64_t bytes) {
+    const uint64_t n = hLen.size();
     ctx->db = std::make_shared<DbStore>();
     // host copy of the lengths drives the stripe table
-    ctx->db->hLengths.resize(n);
-    HIPCHK(hipMemcpy(ctx->db->hLengths.data(), dLen, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    ctx->db->hLengths = std::move(hLen);
     const uint32_t nStripes = (uint32_t) ((n + kStripeTargets - 1) / kStripeTargets);
     std::vector<uint64_t> sOff(nStripes);
     std::vector<uint32_t> sLen(nStripes), sCols(nStripes);
@@ -73,8 +87,7 @@ static int buildDb(fsgpu_ctx *ctx, const uint8_t *dRaw3di, const uint8_t *dRawAA
     for (uint32_t s = 0; s < nStripes; s++) {
         int mx = 0;
         for (uint64_t k = (uint64_t) s * 8; k < std::min<uint64_t>(n, (uint64_t) s * 8 + 8); k++) {
-            int L = ctx->db->hLengths[sTargets[k]];
-            if (L < 0 || L > FSGPU_MAX_SEQ_LEN) { ctx->err = "target length out of range"; return FSGPU_E_ARG; }
+            const int L = ctx->db->hLengths[sTargets[k]];          // 0 .. FSGPU_MAX_SEQ_LEN: checkTable
             mx = std::max(mx, L);
             residues += (uint64_t) L;
         }
@@ -109,13 +122,14 @@ static int buildDb(fsgpu_ctx *ctx, const uint8_t *dRaw3di, const uint8_t *dRawAA
                            (uint32_t) n, ctx->db->stripeOff, ctx->db->stripeLen, ctx->db->stripeTargets, ctx->db->scan);
         HIPCHK(hipGetLastError());
     }
+    // a database without a single residue (bytes == 0) still owns its buffers: "no buffer" means "no database" / "no AA half" to the entries
+    HIPCHK(hipMalloc((void **) &ctx->db->raw3di, std::max<uint64_t>(bytes, 1)));
+    if (dRawAA) HIPCHK(hipMalloc((void **) &ctx->db->alnAA, std::max<uint64_t>(bytes, 1)));
     if (bytes) {
-        HIPCHK(hipMalloc((void **) &ctx->db->raw3di, bytes));
         HIPCHK(hipMemcpyAsync(ctx->db->raw3di, dRaw3di, bytes, hipMemcpyDeviceToDevice, ctx->stream));
         hipLaunchKernelGGL(k_db_unmask, dim3(2048), dim3(256), 0, ctx->stream, dRaw3di, ctx->db->aln3di, bytes);
         HIPCHK(hipGetLastError());
         if (dRawAA) {
-            HIPCHK(hipMalloc((void **) &ctx->db->alnAA, bytes));
             hipLaunchKernelGGL(k_db_unmask, dim3(2048), dim3(256), 0, ctx->stream, dRawAA, ctx->db->alnAA, bytes);
             HIPCHK(hipGetLastError());
         }
@@ -127,43 +141,82 @@ static int buildDb(fsgpu_ctx *ctx, const uint8_t *dRaw3di, const uint8_t *dRawAA
     return FSGPU_OK;
 }
 
+// every way out of a failed load or adopt: the context is left without a database, whatever the reason (the message of the failure is kept)
+static int dropDb(fsgpu_ctx *ctx, int rc) {
+    const std::string why = ctx->err;
+    (void) hipStreamSynchronize(ctx->stream);
+    freeDb(ctx);
+    ctx->err = why;
+    return rc;
+}
+static int dropDbHip(fsgpu_ctx *ctx, const char *what, hipError_t e) {
+    ctx->err = std::string(what) + ": " + hipGetErrorString(e);
+    return dropDb(ctx, FSGPU_E_HIP);
+}
+#define DROPCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return dropDbHip(ctx, #call, e_); } while (0)
+
+// the context lets go of its database, then takes the new one
+static int replaceDb(fsgpu_ctx *ctx, const void *d3, const void *dA, const void *dOff, const void *dLen, std::vector<int32_t> &&hLen, uint64_t bytes) {
+    DROPCHK(hipStreamSynchronize(ctx->stream));
+    freeDb(ctx);
+    int rc = buildDb(ctx, (const uint8_t *) d3, (const uint8_t *) dA, (const uint64_t *) dOff, (const int32_t *) dLen, std::move(hLen), bytes);
+    if (rc != FSGPU_OK) { const std::string why = ctx->err; freeDb(ctx); ctx->err = why; }
+    return rc;
+}
+
 extern "C" {
+
+int64_t fsgpu_db_check_table(const uint64_t *offsets, const int32_t *lengths, uint64_t n, uint64_t bytes) {
+    return fsDbCheckTable(offsets, lengths, n, bytes);
+}
 
 int fsgpu_db_adopt_device(fsgpu_ctx *ctx, const void *d3, const void *dA, const void *dOff, const void *dLen,
                           uint64_t n, uint64_t bytes) {
     if (!ctx) return FSGPU_E_ARG;
-    if (!d3 || !dOff || !dLen || n == 0 || n > 0xfffffff0ull) { ctx->err = "fsgpu_db_adopt_device: bad argument"; return FSGPU_E_ARG; }
-    HIPCHK(hipSetDevice(ctx->device));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    freeDb(ctx);
-    int rc = buildDb(ctx, (const uint8_t *) d3, (const uint8_t *) dA, (const uint64_t *) dOff, (const int32_t *) dLen, n, bytes);
-    if (rc != FSGPU_OK) freeDb(ctx);
-    return rc;
+    DROPCHK(hipSetDevice(ctx->device));
+    if (!d3 || !dOff || !dLen || n == 0 || n > 0xfffffff0ull) { ctx->err = "fsgpu_db_adopt_device: bad argument"; return dropDb(ctx, FSGPU_E_ARG); }
+    // the table comes to the host before anything is freed or launched: every kernel reads data[offsets[t] + col], col < lengths[t], unguarded
+    // (through one pinned block: a copy into pageable memory of this size is several times slower and varies from call to call)
+    struct Pinned {
+        void *p = nullptr;
+        ~Pinned() { if (p) (void) hipHostFree(p); }
+    } pin;
+    DROPCHK(hipHostMalloc(&pin.p, (n + 1) * sizeof(uint64_t) + n * sizeof(int32_t)));
+    uint64_t *hOff = (uint64_t *) pin.p;
+    int32_t *hl = (int32_t *) (hOff + n + 1);
+    DROPCHK(hipMemcpy(hOff, dOff, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    DROPCHK(hipMemcpy(hl, dLen, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    const int rc = checkTable(ctx, "fsgpu_db_adopt_device", hOff, hl, n, bytes);
+    if (rc != FSGPU_OK) return dropDb(ctx, rc);
+    std::vector<int32_t> hLen(hl, hl + n);
+    return replaceDb(ctx, d3, dA, dOff, dLen, std::move(hLen), bytes);
 }
 
 int fsgpu_db_load(fsgpu_ctx *ctx, const uint8_t *data3di, const uint8_t *dataAA, const uint64_t *offsets,
                   const int32_t *lengths, uint64_t n, uint64_t bytes) {
     if (!ctx) return FSGPU_E_ARG;
-    if (!data3di || !offsets || !lengths || n == 0) { ctx->err = "fsgpu_db_load: bad argument"; return FSGPU_E_ARG; }
-    HIPCHK(hipSetDevice(ctx->device));
-    uint8_t *r3 = nullptr, *rA = nullptr;
-    uint64_t *dO = nullptr;
-    int32_t *dL = nullptr;
-    HIPCHK(hipMalloc((void **) &r3, std::max<uint64_t>(bytes, 1)));
-    HIPCHK(hipMemcpy(r3, data3di, bytes, hipMemcpyHostToDevice));
-    if (dataAA) {
-        HIPCHK(hipMalloc((void **) &rA, std::max<uint64_t>(bytes, 1)));
-        HIPCHK(hipMemcpy(rA, dataAA, bytes, hipMemcpyHostToDevice));
-    }
-    HIPCHK(hipMalloc((void **) &dO, (n + 1) * sizeof(uint64_t)));
-    HIPCHK(hipMemcpy(dO, offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
-    HIPCHK(hipMalloc((void **) &dL, n * sizeof(int32_t)));
-    HIPCHK(hipMemcpy(dL, lengths, n * sizeof(int32_t), hipMemcpyHostToDevice));
-    int rc = fsgpu_db_adopt_device(ctx, r3, rA, dO, dL, n, bytes);
-    hipFree(r3); hipFree(rA); hipFree(dO); hipFree(dL);
-    return rc;
+    DROPCHK(hipSetDevice(ctx->device));
+    if (!data3di || !offsets || !lengths || n == 0 || n > 0xfffffff0ull) { ctx->err = "fsgpu_db_load: bad argument"; return dropDb(ctx, FSGPU_E_ARG); }
+    int rc = checkTable(ctx, "fsgpu_db_load", offsets, lengths, n, bytes);
+    if (rc != FSGPU_OK) return dropDb(ctx, rc);
+    // staging copies of the caller's arrays; released on every way out
+    struct Staging {
+        void *p[4] = {nullptr, nullptr, nullptr, nullptr};
+        ~Staging() { for (void *q : p) (void) hipFree(q); }
+    } st;
+    auto stage = [&](int k, const void *src, uint64_t size) -> hipError_t {
+        hipError_t e = hipMalloc(&st.p[k], std::max<uint64_t>(size, 1));
+        return e != hipSuccess || size == 0 ? e : hipMemcpy(st.p[k], src, size, hipMemcpyHostToDevice);
+    };
+    hipError_t e = stage(0, data3di, bytes);
+    if (e == hipSuccess && dataAA) e = stage(1, dataAA, bytes);
+    if (e == hipSuccess) e = stage(2, offsets, (n + 1) * sizeof(uint64_t));
+    if (e == hipSuccess) e = stage(3, lengths, n * sizeof(int32_t));
+    if (e != hipSuccess) return dropDbHip(ctx, "fsgpu_db_load: staging the database", e);
+    return replaceDb(ctx, st.p[0], st.p[1], st.p[2], st.p[3], std::vector<int32_t>(lengths, lengths + n), bytes);
 }
 
+#undef DROPCHK
 } // extern "C"
 
 // ------------------------------------------------------------------------------------------------------------
@@ -239,18 +292,19 @@ extern "C" int fsgpu_db_broadcast(fsgpu_ctx *src, fsgpu_ctx **dst, int n, int *u
     const DbStore &db = *src->db;
     const uint64_t nT = db.n, bytes = db.bytes;
     // the four inputs of buildDb as they live on the source device (the unmasked AA copy is a fixed point of k_db_unmask)
-    struct Buf { const void *srcp; size_t size; std::vector<void *> dstp; };
-    Buf bufs[4] = {{db.raw3di, (size_t) bytes, {}}, {db.hasAA ? db.alnAA : nullptr, db.hasAA ? (size_t) bytes : 0, {}},
-                   {db.dOffsets, (size_t) (nT + 1) * sizeof(uint64_t), {}}, {db.dLengths, (size_t) nT * sizeof(int32_t), {}}};
+    // (a database without residues has bytes == 0: its two byte buffers are still allocated on the destination, nothing is copied into them)
+    struct Buf { const void *srcp; size_t size; bool present; std::vector<void *> dstp; };
+    Buf bufs[4] = {{db.raw3di, (size_t) bytes, true, {}}, {db.hasAA ? db.alnAA : nullptr, db.hasAA ? (size_t) bytes : 0, db.hasAA, {}},
+                   {db.dOffsets, (size_t) (nT + 1) * sizeof(uint64_t), true, {}}, {db.dLengths, (size_t) nT * sizeof(int32_t), true, {}}};
     auto freeAll = [&]() {
         for (Buf &b : bufs) for (size_t i = 0; i < b.dstp.size(); i++) if (b.dstp[i]) { (void) hipSetDevice(dst[i]->device); (void) hipFree(b.dstp[i]); }
         (void) hipSetDevice(src->device);
     };
     for (Buf &b : bufs) {
         b.dstp.assign(n, nullptr);
-        if (!b.size) continue;
+        if (!b.present) continue;
         for (int i = 0; i < n; i++) {
-            if (hipSetDevice(dst[i]->device) != hipSuccess || hipMalloc(&b.dstp[i], b.size) != hipSuccess) { freeAll(); src->err = "fsgpu_db_broadcast: out of device memory"; return FSGPU_E_NOMEM; }
+            if (hipSetDevice(dst[i]->device) != hipSuccess || hipMalloc(&b.dstp[i], std::max<size_t>(b.size, 1)) != hipSuccess) { freeAll(); src->err = "fsgpu_db_broadcast: out of device memory"; return FSGPU_E_NOMEM; }
         }
     }
     HIPCHK(hipSetDevice(src->device));

@@ -67,7 +67,9 @@ __global__ __launch_bounds__(256) void k_diag_rescore(DiagArgs a) {
     const int diagonal = p.diagonal;
     const int dist = diagonal < 0 ? -diagonal : diagonal;
     int s = 0, e = 0;
-    if (diagonal >= 0 && dist < Lq) {
+    if (Lt == 0) {
+        // a target without residues has no cell on any diagonal (the reference would compare the byte behind it for identicalAA): no overlap
+    } else if (diagonal >= 0 && dist < Lq) {
         const int len = min(Lt, Lq - dist);
         r.diagonalLen = len;
         r.score = kadane(len, [&](int pos) { return (int) m3[q3[dist + pos] * kAlphabet + t3[pos]] + (int) mA[qA[dist + pos] * kAlphabet + tA[pos]]; }, s, e);

@@ -103,7 +103,9 @@ extern "C" int64_t fsgpu_gapless_item_records(const uint64_t *items, uint64_t nI
     return (int64_t) nItems;
 }
 
-static int gaplessItems(fsgpu_ctx *ctx, int ov, const uint4 **items, uint32_t *nItems, bool *anySplit) {
+// *needsClear: the score bytes must be zeroed before the launch -- column segments combine by atomic max into them, and a stripe of eight targets
+// without residues has no work item at all, so nothing would store its bytes
+static int gaplessItems(fsgpu_ctx *ctx, int ov, const uint4 **items, uint32_t *nItems, bool *needsClear) {
     DbStore &db = *ctx->db;
     std::lock_guard<std::mutex> lock(db.itemMutex);
     DbStore::ItemList &l = db.itemLists[ov];
@@ -121,9 +123,10 @@ static int gaplessItems(fsgpu_ctx *ctx, int ov, const uint4 **items, uint32_t *n
             const hipError_t ce = hipMemcpy(l.items, rec.data(), rec.size() * sizeof(uint4), hipMemcpyHostToDevice);
             if (ce != hipSuccess) { (void) hipFree(l.items); l.items = nullptr; ctx->err = std::string("hipMemcpy(work items): ") + hipGetErrorString(ce); return FSGPU_E_HIP; }
         }
-        l.n = (uint32_t) v.size(); l.split = split; l.built = true;
+        const bool emptyStripe = std::find(len.begin(), len.end(), 0u) != len.end();
+        l.n = (uint32_t) v.size(); l.needsClear = split || emptyStripe; l.built = true;
     }
-    *items = l.items; *nItems = l.n; *anySplit = l.split;
+    *items = l.items; *nItems = l.n; *needsClear = l.needsClear;
     return FSGPU_OK;
 }
 
@@ -291,25 +294,26 @@ static int mqScan(fsgpu_ctx *ctx, const MqBatch &b) {
     if (!ctx->scanDoneEv) HIPCHK(hipEventCreateWithFlags(&ctx->scanDoneEv, hipEventDisableTiming));
     struct Launch { GaplessLaunchFn fn; const uint4 *items; uint32_t nItems; size_t rec0; int count; };
     std::vector<Launch> launches;
-    bool anySplit = false, split = false;
+    bool anyClear = false, clear = false;
     for (int k0 = 0; k0 < b.nb;) {
         const int R = b.classOf(k0), k1 = b.classEnd(k0);
         int kFree = k0;                                   // the paired queries of a class are its first ones
         while (kFree < k1 && b.isPaired[kFree]) kFree++;
         Launch l{kGaplessUntiled[R], nullptr, 0, (size_t) kFree, k1 - kFree};
-        if ((rc = gaplessItems(ctx, R, &l.items, &l.nItems, &split)) != FSGPU_OK) return rc;
-        anySplit = anySplit || split;
+        if ((rc = gaplessItems(ctx, R, &l.items, &l.nItems, &clear)) != FSGPU_OK) return rc;
+        anyClear = anyClear || clear;
         if (kFree < k1) launches.push_back(l);
         k0 = k1;
     }
     for (const MqBatch::PairLaunch &pl : b.pairLaunches) {
         Launch l{kGaplessPaired[pl.Rq], nullptr, 0, pl.rec0, pl.count};
-        if ((rc = gaplessItems(ctx, pl.Rq, &l.items, &l.nItems, &split)) != FSGPU_OK) return rc;     // warm-up of a column segment = the QUERY's rows
+        if ((rc = gaplessItems(ctx, pl.Rq, &l.items, &l.nItems, &clear)) != FSGPU_OK) return rc;     // warm-up of a column segment = the QUERY's rows
+        anyClear = anyClear || clear;                     // (the loop above has asked for every class already, paired or not; kept so that this does not depend on it)
         launches.push_back(l);
     }
-    // column segments combine by atomic max into zeroed score bytes: clear all slices BEFORE the first launch (a memset
-    // between launches would wipe what earlier groups stored)
-    if (anySplit) HIPCHK(hipMemsetAsync(ctx->mqScores.p, 0, b.scoreStride * b.nb, ctx->stream));
+    // column segments combine by atomic max into zeroed score bytes, stripes without a column store nothing: clear all slices BEFORE the
+    // first launch (a memset between launches would wipe what earlier groups stored)
+    if (anyClear) HIPCHK(hipMemsetAsync(ctx->mqScores.p, 0, b.scoreStride * b.nb, ctx->stream));
     std::lock_guard<std::mutex> scanLock(ctx->db->scanMutex);
     if (ctx->db->lastScanDone && ctx->db->lastScanDone != ctx->scanDoneEv) HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->db->lastScanDone, 0));
     HIPCHK(hipEventRecord(ctx->ev[0], ctx->stream));
@@ -380,13 +384,13 @@ int fsgpu_gapless_launch(fsgpu_ctx *ctx, const int8_t *pssm, int L, int scoreCap
     GaplessArgs ga;
     ga.queries = nullptr; ga.blocksPerQuery = 0;
     ga.scan = ctx->db->scan; ga.stripeOff = ctx->db->stripeOff; ga.stripeLen = ctx->db->stripeLen; ga.stripeTargets = ctx->db->stripeTargets;
-    bool anySplit = false;
-    if ((rc = gaplessItems(ctx, nTiles > 1 ? 0 : R, &ga.items, &ga.nItems, &anySplit)) != FSGPU_OK) return rc;
+    bool needsClear = false;
+    if ((rc = gaplessItems(ctx, nTiles > 1 ? 0 : R, &ga.items, &ga.nItems, &needsClear)) != FSGPU_OK) return rc;
     ga.nTargets = n; ga.pssm = (const int8_t *) ctx->pssm.p; ga.L = L;
     ga.cap = std::max(0, std::min(scoreCap, 255));
     ga.scores = (uint8_t *) ctx->scores.p; ga.queue = ctx->queue;
     ga.tileBase = 0; ga.firstTile = 1; ga.lastTile = 1; ga.borderIn = nullptr; ga.borderOut = nullptr; ga.scoreAcc = (int16_t *) ctx->scoreAcc.p;
-    if (anySplit) HIPCHK(hipMemsetAsync(ctx->scores.p, 0, n, ctx->stream));     // column segments combine by atomic max
+    if (needsClear) HIPCHK(hipMemsetAsync(ctx->scores.p, 0, n, ctx->stream));     // column segments combine by atomic max; a stripe without columns stores nothing
     HIPCHK(hipEventRecord(ctx->ev[0], ctx->stream));
     if (nTiles == 1) {
         HIPCHK(hipMemsetAsync(ctx->queue, 0, 4, ctx->stream));

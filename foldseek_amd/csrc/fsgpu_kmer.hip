@@ -185,6 +185,7 @@ int fsgpu_kmer_index_build(fsgpu_ctx *ctx, const fsgpu_kmer_index_params *p, con
     if (p->kmerSize != 6) { ctx->err = "k-mer prefilter: only k = 6 is implemented on the device"; return FSGPU_E_UNSUPPORTED; }
     // UngappedAlignment switches to computeLongScore (wrapped 16-bit diagonals) from 32768 residues on (UngappedAlignment.cpp:198,295-312)
     if (ctx->db->maxLen >= 32768) { ctx->err = "k-mer prefilter: targets of 32768 residues or more are not supported on the device"; return FSGPU_E_UNSUPPORTED; }
+    if (ctx->db->residues == 0) { ctx->err = "k-mer prefilter: the database holds no residues, there is nothing to index"; return FSGPU_E_UNSUPPORTED; }
     RPCHK(hipSetDevice(ctx->device));
     std::shared_ptr<KmerIndex> ix = std::make_shared<KmerIndex>();
     ix->p = *p; ix->db = ctx->db; ix->n = ctx->db->n;

@@ -87,8 +87,8 @@ __global__ void k_kmer_mask(const uint8_t *raw, const uint64_t *offsets, const i
             for (int i = startOfRepeat; i < L; ++i) dst[i] = 20;
     }
     if (maskLower) for (int i = 0; i < L; i++) if (src[i] >= 32) dst[i] = 20;
-    const int padded = (L + 3) & ~3;
-    for (int i = L; i < padded; i++) dst[i] = 20;
+    // nothing behind the entry is written: the buffer was filled with X before the launch, and in a table packed without padding the next
+    // byte is another entry's first residue
 }
 
 // one (k-mer, seqId<<16|pos) pair per residue start position, in (seqId, pos) order; non-k-mers get kKmerInvalid.

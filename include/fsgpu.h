@@ -106,13 +106,37 @@ void *fsgpu_stream(const fsgpu_ctx *ctx);
  * (M/src/util/makepaddedseqdb.cpp:59-109): numeric codes 0..20, +32 when soft-masked, entries padded with 20.
  * offsets[n+1] in bytes (offsets[n] = end), lengths[n] = residues per entry (index length - 2).
  * dataAA may be NULL (prefilter only).  Pointers are borrowed for the duration of the call; the DB is copied to HBM
- * and re-tiled there (coalesced 8-target stripes for the scan, plain unmasked copies for the aligner). */
+ * and re-tiled there (coalesced 8-target stripes for the scan, plain unmasked copies for the aligner).
+ * The table contract.  Every kernel reads data[offsets[t] + col] for col < lengths[t] and nothing else guards it, so the table is checked
+ * (fsgpu_db_check_table) before anything is allocated or launched: 0 <= lengths[t] <= FSGPU_MAX_SEQ_LEN, offsets[t] + lengths[t] <= bytes
+ * (tested without forming the sum), offsets[n] <= bytes, and no two entries share a byte (the k-mer index build writes a masked copy of every
+ * entry in place: two entries over one byte would be two writers).  Nothing else is asked of the layout: entries may lie in any memory
+ * order (descending included), at offsets that are no multiple of 4, with no padding at all or with gaps of any size between them -- bytes
+ * outside every entry are never read -- and in any order of length (the scan groups the targets by length itself).  An entry may be empty
+ * (lengths[t] == 0, any offset up to bytes), and so may the whole buffer (bytes == 0); what the entries answer for such a target is said
+ * below.  A bad table is FSGPU_E_ARG with a message that names the first bad entry.  A call that fails -- a refused table, a bad argument
+ * (n == 0 is one), a HIP call that fails at any point of the load -- leaves the context WITHOUT a database (every entry then answers
+ * FSGPU_E_NODB) and holds no device memory of the attempt; the next good load works.
+ * A target without residues: the scan scores it 0; the Smith-Waterman entries answer (0, 0, 0, word 1); fsgpu_diag_rescore answers
+ * FSGPU_DIAG_NO_OVERLAP on every diagonal; fsgpu_block_backtrace refuses a task on it (no end cell exists: FSGPU_E_ARG); the k-mer index
+ * holds nothing of it.  A database of nothing but such targets loads, scans and aligns like any other; fsgpu_kmer_index_build refuses it
+ * by name (FSGPU_E_UNSUPPORTED: nothing to index).
+ * Bytes outside 0..20 and 32..52: the scan copy reads every byte above 20 as X; the aligner copies take 32 off a byte of 32 or more and
+ * read what is then above 20 as X; the k-mer index's copy does the same and then, with maskLowerCase, reads every byte that was 32 or more as X. */
 int fsgpu_db_load(fsgpu_ctx *ctx, const uint8_t *data3di, const uint8_t *dataAA,
                   const uint64_t *offsets, const int32_t *lengths, uint64_t n, uint64_t bytes);
 /* Same, but the four buffers already live in this device's HBM (e.g. filled by an RCCL broadcast over xGMI).
- * The context does not take ownership of them and does not need them after the call returns. */
+ * The caller's writes to them must be COMPLETE before the call (synchronise the stream or device that filled them: the call reads them on
+ * the context's own stream and copies the table to the host, ordered against nobody else's work).  The context does not take ownership of
+ * them and does not need them after the call returns: they may be overwritten or freed at once.  Same table contract, same refusals. */
 int fsgpu_db_adopt_device(fsgpu_ctx *ctx, const void *d_data3di, const void *d_dataAA,
                           const void *d_offsets, const void *d_lengths, uint64_t n, uint64_t bytes);
+/* Host-only (no device call): the table contract above for host arrays.  -1 for a good table, else the index of the first bad entry: the
+ * lowest t whose length is outside 0 .. FSGPU_MAX_SEQ_LEN, which lies outside the buffer (offsets[t] > bytes || lengths[t] > bytes -
+ * offsets[t]), or which begins inside the bytes of another entry (of two entries that begin at one address, the later one; entries
+ * without residues hold no byte); n when only offsets[n] > bytes.  A NULL offsets, or a NULL lengths with n > 0, is no table at all: the
+ * answer is 0, as for a bad first entry (n == 0 with offsets[0] <= bytes is a good table; the load entries refuse n == 0 themselves). */
+int64_t fsgpu_db_check_table(const uint64_t *offsets, const int32_t *lengths, uint64_t n, uint64_t bytes);
 uint64_t fsgpu_db_size(const fsgpu_ctx *ctx);      /* entries */
 uint64_t fsgpu_db_residues(const fsgpu_ctx *ctx);  /* sum of lengths */
 
@@ -244,7 +268,7 @@ typedef struct {
 } fsgpu_diag_pair;
 enum {
     FSGPU_DIAG_OK = 0,
-    FSGPU_DIAG_NO_OVERLAP = 1,   /* |diagonal| beyond the sequence: the reference keeps LocalAlignment's defaults (-1, -1, 0) */
+    FSGPU_DIAG_NO_OVERLAP = 1,   /* |diagonal| beyond the sequence, or a target without residues: the reference keeps LocalAlignment's defaults (-1, -1, 0) */
     FSGPU_DIAG_UNDEFINED = 2,    /* negative diagonal with a target longer than the query: the reference's reverse pass reads
                                     past the query (structurerescorediagonal.cpp:96-99); forward fields are valid, revScore is not */
     FSGPU_DIAG_BAD_ID = 3
@@ -352,7 +376,8 @@ typedef struct {
  * (the 8-bit "k-mer" matrix of the prefilter: SubstitutionMatrix(3di.out, 8.0, -0.2), int16 row-major 21x21).
  * Limits (FSGPU_E_UNSUPPORTED beyond them): k = 6; fewer than 2^32 residues in the database (the reference switches to k = 7 from 3.35e9 residues
  * on, IndexTable.h:456-458, before that limit is reached); at most 33.5 M targets (512 coarse bins of the hit-stream partition, each inside one block of
- * 65536 target ids; 16.4 M until round 5); no target of 32768 residues or more.  Index entries are 4 bytes (seqId << posBits | position) while the id
+ * 65536 target ids; 16.4 M until round 5); no target of 32768 residues or more (so a position never needs a 16th bit: 15 at most in either entry form);
+ * at least one residue in the database.  Index entries are 4 bytes (seqId << posBits | position) while the id
  * bits and the position bits of the database fit 32 together, 8 bytes otherwise. */
 int fsgpu_kmer_index_build(fsgpu_ctx *ctx, const fsgpu_kmer_index_params *p, const int16_t *kmerSubMat21x21);
 uint64_t fsgpu_kmer_index_entries(const fsgpu_ctx *ctx);
