@@ -150,6 +150,7 @@ def lib():
         "fsgpu_kmer_index_build": (i32, [vp, vp, vp]),
         "fsgpu_kmer_index_entries": (u64, [vp]),
         "fsgpu_kmer_index_entry_bytes": (i32, [vp]),
+        "fsgpu_kmer_index_get_params": (i32, [vp, C.POINTER(KmerIndexParams)]),
         "fsgpu_kmer_search": (i32, [vp, vp, vp, i32, vp, vp, vp, vp]),
         "fsgpu_kmer_index_copy": (i32, [vp, vp, vp, vp]),
         "fsgpu_kmer_row_copy": (i32, [vp, i32, vp, vp]),
@@ -222,7 +223,7 @@ def exported_symbols():
             "fsgpu_db_adopt_device", "fsgpu_db_check_table", "fsgpu_db_size", "fsgpu_db_residues", "fsgpu_gapless_scan", "fsgpu_gapless_scores",
             "fsgpu_gapless_launch", "fsgpu_gapless_finish", "fsgpu_sw_batch", "fsgpu_sw_multi", "fsgpu_sw_multi_dir", "fsgpu_sw_multi_dir_c", "fsgpu_sw_multi_c", "fsgpu_sw_launch", "fsgpu_sw_finish",
             "fsgpu_db_broadcast", "fsgpu_rccl_selfcheck", "fsgpu_device_count", "fsgpu_live_devices", "fsgpu_gapless_plan_items", "fsgpu_gapless_item_records", "fsgpu_block_backtrace", "fsgpu_block_backtrace_footprint",
-            "fsgpu_lddt_batch", "fsgpu_tm_batch", "fsgpu_last_kernel_ms", "fsgpu_history_counters", "fsgpu_sw_last_passes", "fsgpu_sw3_last_plan", "fsgpu_kmer_index_build", "fsgpu_kmer_index_entries", "fsgpu_kmer_index_entry_bytes", "fsgpu_kmer_search",
+            "fsgpu_lddt_batch", "fsgpu_tm_batch", "fsgpu_last_kernel_ms", "fsgpu_history_counters", "fsgpu_sw_last_passes", "fsgpu_sw3_last_plan", "fsgpu_kmer_index_build", "fsgpu_kmer_index_entries", "fsgpu_kmer_index_entry_bytes", "fsgpu_kmer_index_get_params", "fsgpu_kmer_search",
             "fsgpu_kmer_index_copy", "fsgpu_kmer_row_copy", "fsgpu_kmer_last_counts", "fsgpu_kmer_last_segments", "fsgpu_kmer_plan_coarse", "fsgpu_kmer_batch_hint",
             "fsgpu_diag_rescore", "fsgpu_sw_batch_seqs"]
 
@@ -438,6 +439,14 @@ class Context:
     def kmer_index_entry_bytes(self):
         """4: an index entry is seqId << posBits | position in 32 bits; 8: seqId << 16 | position in 64 (0 before the index is built)"""
         return lib().fsgpu_kmer_index_entry_bytes(self.h)
+
+    def kmer_index_params(self):
+        """fsgpu_kmer_index_get_params: the parameters of the resident index as a dict; raises while there is none"""
+        p = KmerIndexParams()
+        rc = lib().fsgpu_kmer_index_get_params(self.h, C.byref(p))
+        if rc != 0:
+            raise FsgpuError(f"fsgpu_kmer_index_get_params rc={rc}: no k-mer index")
+        return {n: int(getattr(p, n)) for n, _ in KmerIndexParams._fields_}
 
     def kmer_index_copy(self, nbytes_db):
         off = np.zeros(64000001, np.uint32)
@@ -894,10 +903,12 @@ class Search:
         return out
 
     def kmer_batch(self, m_kmer, m_ungapped, kmer_thr, spaced, qaa_ptrs, q3_ptrs, lens, pref_identity=None, aln_identity=None, max_res=200, min_diag=30,
-                   kmer_score_only=False):
+                   kmer_score_only=False, rows=None):
         """fshost_search_kmer_batch: k-mer prefilter + coverage pre-filter + structure alignment of a batch of queries in ONE library call (the per-batch
         body of the `search` module).  qaa_ptrs / q3_ptrs: uint64 arrays with the host addresses of the queries' code strings (0..20), lens: their lengths.
-        Returns a dict: nhits, status, nkept, nres (int32[nq]), hits [nq, max_res], kept [nq, max_res], results [nq, max_res * (1 + alt)], seconds[4]."""
+        Returns a dict: nhits, status, nkept, nres (int32[nq]), hits [nq, max_res], kept [nq, max_res], results [nq, max_res * (1 + alt)], seconds[4].
+        rows: that many rows per output array instead of max(nq, 1) (tests: rows behind the last query that the call must leave alone); the arrays start
+        out as bytes of 0xA5 then, not as zeros."""
         nq = len(lens)
         pa = np.ascontiguousarray(qaa_ptrs, np.uint64); p3 = np.ascontiguousarray(q3_ptrs, np.uint64)
         Ls = np.ascontiguousarray(lens, np.int32)
@@ -905,10 +916,16 @@ class Search:
         ai = None if aln_identity is None else np.ascontiguousarray(aln_identity, np.int64)
         sp = KmerSearchParams(max_res, min_diag, 0, 1 if kmer_score_only else 0, 0, 0, 0)
         rcap = max_res * (1 + max(0, self.par.altAlignment))
-        n1 = max(nq, 1)
-        out = {"hits": np.zeros((n1, max_res), KMER_HIT_DT), "nhits": np.zeros(n1, np.int32), "status": np.zeros(n1, np.int32),
-               "kept": np.zeros((n1, max_res), np.uint32), "nkept": np.zeros(n1, np.int32), "results": np.zeros((n1, rcap), RESULT_DT),
-               "nres": np.zeros(n1, np.int32), "seconds": np.zeros(4)}
+        n1 = max(nq, 1) if rows is None else max(nq, 1, int(rows))
+
+        def new(shape, dt):
+            a = np.zeros(shape, dt)
+            if rows is not None:
+                a.view(np.uint8)[...] = 0xA5
+            return a
+        out = {"hits": new((n1, max_res), KMER_HIT_DT), "nhits": new(n1, np.int32), "status": new(n1, np.int32),
+               "kept": new((n1, max_res), np.uint32), "nkept": new(n1, np.int32), "results": new((n1, rcap), RESULT_DT),
+               "nres": new(n1, np.int32), "seconds": np.zeros(4)}
         rc = lib().fshost_search_kmer_batch(self.h, m_kmer.h, m_ungapped.h, C.cast(C.byref(sp), C.c_void_p), int(kmer_thr), int(spaced), nq, _ptr(pa), _ptr(p3), _ptr(Ls),
                                             _ptr(pi), _ptr(ai), _ptr(out["hits"]), _ptr(out["nhits"]), _ptr(out["status"]), _ptr(out["kept"]), _ptr(out["nkept"]),
                                             _ptr(out["results"]), _ptr(out["nres"]), _ptr(out["seconds"]))

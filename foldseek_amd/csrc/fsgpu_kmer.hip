@@ -225,6 +225,12 @@ extern "C" {
 
 uint64_t fsgpu_kmer_index_entries(const fsgpu_ctx *ctx) { return ctx && ctx->kidx ? ctx->kidx->nEntries : 0; }
 int fsgpu_kmer_index_entry_bytes(const fsgpu_ctx *ctx) { return ctx && ctx->kidx ? (ctx->kidx->posBits ? 4 : 8) : 0; }
+int fsgpu_kmer_index_get_params(const fsgpu_ctx *ctx, fsgpu_kmer_index_params *out) {
+    if (!ctx || !out) return FSGPU_E_ARG;
+    if (!ctx->kidx) return FSGPU_E_NODB;          // (ctx is const: the text of this refusal is the caller's to write)
+    *out = ctx->kidx->p;
+    return FSGPU_OK;
+}
 
 int fsgpu_kmer_index_build(fsgpu_ctx *ctx, const fsgpu_kmer_index_params *p, const int16_t *kmerSub) {
     if (!ctx || !p || !kmerSub) return FSGPU_E_ARG;

@@ -1072,6 +1072,14 @@ int fshost_search_kmer_batch(fshost_search *s, const fshost_matrix *mKmer, const
                              uint32_t *keptIds, int32_t *nkept, fshost_result *results, int32_t *nres, double *seconds) {
     if (!s || !s->ctx || !mKmer || !mUngapped || !sp || nq < 0 || (nq > 0 && (!qAA || !q3di || !L || !hits || !nhits || !status || !keptIds || !nkept || !results || !nres))) return FSGPU_E_ARG;
     if (sp->maxResListLen <= 0) { s->err = "fshost_search_kmer_batch: maxResListLen >= 1 required"; return FSGPU_E_ARG; }
+    {   // the thresholds prepared below are read by the device with the pattern of the RESIDENT index: another `spaced` here is refused before anything runs
+        fsgpu_kmer_index_params ip;
+        // (without an index fsgpu_kmer_search refuses below, as before)
+        if (fsgpu_kmer_index_get_params(s->ctx, &ip) == FSGPU_OK && (spaced != 0) != (ip.spaced != 0)) {
+            s->err = "fshost_search_kmer_batch: spaced = " + std::to_string(spaced) + " but the resident k-mer index was built with spaced = " + std::to_string(ip.spaced);
+            return FSGPU_E_ARG;
+        }
+    }
     const fshost_params &par = s->par;
     const size_t cap = (size_t) sp->maxResListLen, rcap = cap * (size_t) (1 + std::max(0, par.altAlignment));
     double t0 = nowSec();

@@ -383,6 +383,9 @@ int fsgpu_kmer_index_build(fsgpu_ctx *ctx, const fsgpu_kmer_index_params *p, con
 uint64_t fsgpu_kmer_index_entries(const fsgpu_ctx *ctx);
 /* Bytes of one index entry of the resident index: 4 or 8 (see above; FSGPU_KMER_ENTRY64=1 at build time keeps the 8-byte form); 0 before an index is built. */
 int fsgpu_kmer_index_entry_bytes(const fsgpu_ctx *ctx);
+/* The parameters the resident index was built with (a clone answers with those of the index it shares).  FSGPU_E_NODB while the context has
+ * no index, FSGPU_E_ARG for a null pointer; *out is written only on FSGPU_OK.  What prepares queries for fsgpu_kmer_search reads `spaced` here. */
+int fsgpu_kmer_index_get_params(const fsgpu_ctx *ctx, fsgpu_kmer_index_params *out);
 /* Inspection (tests): copy the offset table (64e6+1 uint32), the entries (seqId << 16 | position) and/or the masked
  * sequence lookup (padded DB layout) to host memory; any pointer may be NULL.  The table is kept in the DEVICE k-mer
  * order: index = first3mer * 8000 + last3mer (the reference numbers k-mers first3mer + 8000 * last3mer).  Row `row` of the extended 3-mer matrix. */
@@ -433,7 +436,11 @@ enum {
 };
 /* Runs nq queries (batched on the device), writes per query q up to maxResListLen hits to out[q*maxResListLen ..],
  * their number to nout[q] and a FSGPU_KMER_* code to status[q]; hits are bit-identical to QueryMatcher::matchQuery
- * (order included) whenever status[q] == 0.  stats (may be NULL): per query kmersPerPos, dbMatches, overflowed, bins. */
+ * (order included) whenever status[q] == 0.  stats (may be NULL): per query kmersPerPos, dbMatches, overflowed, bins.
+ * kmerThr[] of every query must be prepared with the pattern of the RESIDENT index (fsgpu_kmer_index_get_params: 10 residues with spaced = 1,
+ * 6 with spaced = 0): the call reads max(0, L - patternSize + 1) thresholds per query and cannot tell an array prepared for the other pattern --
+ * a shorter one is read past its end, a longer one gives thresholds summed over the wrong residues.  fshost_search_kmer_batch checks its `spaced`
+ * argument against the index and refuses a mismatch. */
 int fsgpu_kmer_search(fsgpu_ctx *ctx, const fsgpu_kmer_search_params *p, const fsgpu_kmer_query *queries, int nq,
                       fsgpu_kmer_hit *out, int32_t *nout, int32_t *status, double *stats);
 

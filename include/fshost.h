@@ -157,7 +157,9 @@ int fshost_search_align_batch(fshost_search *s, int nq, const uint8_t *const *qA
  * structurealign compares with the target's (-1: none).  Outputs, cap = sp->maxResListLen per query: hits [nq * cap] with nhits[q] prefilter hits
  * (before the coverage pre-filter), status[q] (FSGPU_KMER_*), keptIds [nq * cap] with nkept[q] ids handed to the aligner, results
  * [nq * cap * (1 + altAlignment)] with nres[q] accepted alignments (backtraces through fshost_search_backtrace until the next call), seconds[4]:
- * host wall time of prepare / prefilter call / coverage pre-filter / align call.  A query whose status is < 0 gets no alignments.  Returns 0 or < 0. */
+ * host wall time of prepare / prefilter call / coverage pre-filter / align call.  A query whose status is < 0 gets no alignments.  Returns 0 or < 0.
+ * `spaced` must be the value the resident k-mer index was built with (fsgpu_kmer_index_get_params): the thresholds prepared here are read by the device
+ * with the index's pattern.  Another value is refused with FSGPU_E_ARG before anything is prepared or launched; the error text names both values. */
 int fshost_search_kmer_batch(fshost_search *s, const fshost_matrix *mKmer, const fshost_matrix *mUngapped, const fsgpu_kmer_search_params *sp,
                              int kmerThr, int spaced, int nq, const uint8_t *const *qAA, const uint8_t *const *q3di, const int *L,
                              const int64_t *prefIdentity, const int64_t *alnIdentity, fsgpu_kmer_hit *hits, int32_t *nhits, int32_t *status,
