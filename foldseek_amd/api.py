@@ -933,6 +933,39 @@ class Search:
             raise FsgpuError(f"kmer_batch rc={rc}: {lib().fshost_search_error(self.h).decode()}")
         return out
 
+    def set_tm(self, tm_thr=0.0, mode=0, structure_bits=False):
+        """fshost_search_set_tm: --tmscore-threshold, --tmscore-threshold-mode (0 alignment, 1 query, 2 target), --sort-by-structure-bits; call it before
+        bind_ca"""
+        rc = lib().fshost_search_set_tm(self.h, float(tm_thr), int(mode), 1 if structure_bits else 0)
+        if rc != 0:
+            raise FsgpuError(f"set_tm rc={rc}: mode {mode} is none of 0, 1, 2")
+
+    def bind_ca(self, lddt_thr, entries):
+        """fshost_search_bind_ca: --lddt-threshold and the targets' <db>_ca entries (bytes as stored), entries[i] for target INDEX i; entries None unbinds.
+        The packed entries stay alive with this object."""
+        if entries is None:
+            self._ca = None
+            rc = lib().fshost_search_bind_ca(self.h, 0.0, None, None, None)
+        else:
+            lens = np.array([len(e) for e in entries], np.uint32)
+            off = np.zeros(len(entries), np.uint64)
+            off[1:] = np.cumsum(lens[:-1].astype(np.uint64))
+            base = np.frombuffer(b"".join(bytes(e) for e in entries) + b"\0", np.uint8).copy()
+            self._ca = (base, off, lens)
+            rc = lib().fshost_search_bind_ca(self.h, float(lddt_thr), _ptr(base), _ptr(off), _ptr(lens))
+        if rc != 0:
+            raise FsgpuError(f"bind_ca rc={rc}: {lib().fshost_search_error(self.h).decode()}")
+
+    def set_query_ca(self, entries):
+        """fshost_search_set_query_ca: the <db>_ca entries of the queries of the NEXT align / align_batch / kmer_batch call, in their order (consumed by it)"""
+        self._qca = [np.frombuffer(bytes(e) + b"\0", np.uint8).copy() for e in entries]
+        lens = np.array([len(e) for e in entries], np.uint32)
+        P = C.c_void_p * max(len(entries), 1)
+        ptrs = P(*[x.ctypes.data for x in self._qca])
+        rc = lib().fshost_search_set_query_ca(self.h, len(entries), C.cast(ptrs, C.c_void_p), _ptr(lens))
+        if rc != 0:
+            raise FsgpuError(f"set_query_ca rc={rc}")
+
     def startpos_backtrace(self, qAA, q3di, target_id, q_end, db_end, score):
         """alignStartPosBacktrace (SSW-style start + CIGAR: device reverse pass + host banded trace-back); (ok, qStart, dbStart, ids, cigar)"""
         qa, q3 = np.ascontiguousarray(qAA, np.uint8), np.ascontiguousarray(q3di, np.uint8)

@@ -992,8 +992,9 @@ int fshost_search_align_batch(fshost_search *s, int nq, const uint8_t *const *qA
     const double t1 = nowSec();
     // A small batch (the all-vs-all steps: a few thousand pairs per call) is bound by round trips, not by DP cells: both directions of
     // every pair in one submission.  Otherwise: forward pass over every pair, the reversed-query pass only over the pairs whose forward
-    // score passes the gates (3-16 % of a search's hit lists).  FSGPU_SW_ONEPASS_PAIRS overrides the limit (0 = never).
-    static const size_t onePassPairs = [] { const char *e = getenv("FSGPU_SW_ONEPASS_PAIRS"); return e ? (size_t) atoll(e) : (size_t) 16384; }();
+    // score passes the gates (3-16 % of a search's hit lists).  FSGPU_SW_ONEPASS_PAIRS overrides the limit (0 = never; read per call: the tests force
+    // each branch on the same call).
+    const size_t onePassPairs = [] { const char *e = getenv("FSGPU_SW_ONEPASS_PAIRS"); return e ? (size_t) atoll(e) : (size_t) 16384; }();
     int rc;
     if (total > 0 && total <= onePassPairs) {
         rc = fsgpu_sw_multi_c(s->ctx, m3, mA, dq.data(), nq, par.gapOpen, par.gapExtend, s->fwd.data(), s->rev.data());
