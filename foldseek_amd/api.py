@@ -177,6 +177,7 @@ def lib():
         "fshost_evaluer_free": (None, [vp]),
         "fshost_predict_mu_lambda": (None, [vp, vp, C.c_uint, i32, C.POINTER(f64), C.POINTER(f64)]),
         "fshost_evalue_corr": (f64, [vp, f64, f64, f64]),
+        "fshost_evalue_score_cutoff": (i32, [vp, f64, f64, f64]),
         "fshost_params_default": (None, [C.POINTER(Params)]),
         "fshost_search_create": (vp, [vp, C.POINTER(Params), vp, C.c_char_p, vp, vp, vp, vp]),
         "fshost_search_free": (None, [vp]),
@@ -331,6 +332,10 @@ class Evaluer:
 
     def evalue_corr(self, score, lam, mu):
         return lib().fshost_evalue_corr(self.h, float(score), lam, mu)
+
+    def score_cutoff(self, lam, mu, eval_thr):
+        """fshost_evalue_score_cutoff: the smallest integer score in [0, 32767] whose e-value does not exceed eval_thr, 32767 when none does"""
+        return int(lib().fshost_evalue_score_cutoff(self.h, float(lam), float(mu), float(eval_thr)))
 
     def __del__(self):
         if getattr(self, "h", None):

@@ -81,6 +81,16 @@ double Evaluer::computeEvalueCorr(double score, double lambda_, double mu) const
     return pow(evalue, 0.32);
 }
 
+// The first e-value gate of alignStructure (structurealign.cpp:55-59: reject when computeEvalueCorr(score) > evalThr) as a score cutoff: the smallest
+// integer score in [0, 32767] the gate lets through, 32767 when it lets none through.  Found by asking the gate's own function score by score, from 0
+// upwards, never by inverting it: every score below the cutoff is then one the gate rejects, whatever branch of computePvalue it falls in and
+// whether or not the function is monotone there.  (A NaN e-value passes the gate -- `NaN > thr` is false -- and so it ends the search too.)
+int Evaluer::scoreCutoff(double lambda_, double mu, double evalThr) const {
+    for (int s = 0; s < 32767; s++)
+        if (!(computeEvalueCorr((double) s, lambda_, mu) > evalThr)) return s;
+    return 32767;
+}
+
 } // namespace fsh
 
 struct fshost_evaluer { fsh::Evaluer e; };
@@ -97,4 +107,5 @@ void fshost_predict_mu_lambda(const fshost_evaluer *e, const uint8_t *q3di, unsi
     e->e.predictMuLambda(q3di, L, alphabetSize, lambda, mu);
 }
 double fshost_evalue_corr(const fshost_evaluer *e, double score, double lambda, double mu) { return e->e.computeEvalueCorr(score, lambda, mu); }
+int fshost_evalue_score_cutoff(const fshost_evaluer *e, double lambda, double mu, double evalThr) { return e->e.scoreCutoff(lambda, mu, evalThr); }
 }

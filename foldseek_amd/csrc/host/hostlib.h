@@ -33,6 +33,7 @@ struct Evaluer {
     bool load(const char *path, uint64_t dbResidues, std::string &err);
     void predictMuLambda(const uint8_t *seq, unsigned int L, int alphabetSize, double *lambda, double *mu) const;
     double computeEvalueCorr(double score, double lambda, double mu) const;
+    int scoreCutoff(double lambda, double mu, double evalThr) const;
 };
 
 std::string libraryDir();   // directory that holds libfsgpu.so

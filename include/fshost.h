@@ -81,6 +81,12 @@ void fshost_evaluer_free(fshost_evaluer *e);
 void fshost_predict_mu_lambda(const fshost_evaluer *e, const uint8_t *q3di, unsigned int L, int alphabetSize,
                               double *lambda, double *mu);
 double fshost_evalue_corr(const fshost_evaluer *e, double score, double lambda, double mu);
+/* The first e-value gate of alignStructure (structurealign.cpp:55-59) as a score cutoff: the smallest integer s in [0, 32767] with
+ * fshost_evalue_corr(e, s, lambda, mu) <= evalThr (a NaN e-value counts as passing, as it does at the gate), 32767 when there is none.  Found
+ * by evaluating the function at every s from 0 upwards, not by inverting it: every score below the cutoff is one the gate rejects, whatever
+ * branch of computePvalue it falls in.  What a database-wide forward pass needs to drop targets on the device before the aligner sees them
+ * (the exhaustive search, StructureSearch.cpp:114-127; not built yet). */
+int fshost_evalue_score_cutoff(const fshost_evaluer *e, double lambda, double mu, double evalThr);
 
 /* ---- one query through prefilter + structurealign (what bench.py times and the module executables call) ---- */
 typedef struct {
