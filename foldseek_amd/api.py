@@ -54,6 +54,7 @@ DIAG_RES_DT = np.dtype([("score", np.int32), ("startPos", np.int32), ("endPos", 
                         ("identicalAA", np.int32), ("status", np.int32), ("reserved", np.int32)])   # fsgpu_diag_res
 FSGPU_DIAG_OK, FSGPU_DIAG_NO_OVERLAP, FSGPU_DIAG_UNDEFINED, FSGPU_DIAG_BAD_ID = 0, 1, 2, 3
 FSGPU_MAX_SEQ_LEN = 65535      # include/fsgpu.h: the longest query or target an entry takes
+FSGPU_E_ARG, FSGPU_E_UNSUPPORTED = -1, -4
 
 
 class BtQuery(C.Structure):
@@ -906,6 +907,40 @@ class Search:
             bts = [[lib().fshost_search_backtrace(self.h, C.c_void_p(out[i][k:k + 1].ctypes.data)).decode() for k in range(len(out[i]))] for i in range(nq)]
             return out, bts
         return out
+
+    def rescore_diagonal_batch(self, qAAs, q3dis, target_id_lists, diagonal_lists, identity=None):
+        """fshost_search_rescore_diagonal_batch: structurerescorediagonal's per-query body for several queries in ONE library call.  target_id_lists[q] /
+        diagonal_lists[q]: first and third column of query q's prefilter lines in their order (diagonals as the int16 the module reads); identity: per
+        query the target index that is the query itself, -1 for none, or None.  The handle's Params decide the gates; Params.skipUndefinedDiagonals = 1
+        passes over pairs whose reference result is undefined, 0 refuses them (FsgpuError with .rc == FSGPU_E_UNSUPPORTED).
+        Returns (records per query, backtrace strings per query).  Every result buffer has room for n[q] records plus one more and is filled with
+        RESCORE_CANARY bytes before the call; last_rescore = (the whole buffers, nres) is kept for tests that look behind nres[q]."""
+        nq = len(q3dis)
+        qa = [np.ascontiguousarray(x, np.uint8) for x in qAAs]
+        q3 = [np.ascontiguousarray(x, np.uint8) for x in q3dis]
+        ts = [np.ascontiguousarray(x, np.uint32) for x in target_id_lists]
+        ds = [np.ascontiguousarray(x, np.int16) for x in diagonal_lists]
+        if not (len(qa) == len(ts) == len(ds) == nq) or any(len(t) != len(d) for t, d in zip(ts, ds)) or any(len(a) != len(b) for a, b in zip(qa, q3)):
+            raise ValueError("rescore_diagonal_batch: one AA / 3Di query, one id list and one diagonal list of equal length per query")
+        res = [np.frombuffer(bytearray([self.RESCORE_CANARY]) * ((len(t) + 1) * RESULT_DT.itemsize), RESULT_DT) for t in ts]
+        P = C.c_void_p * max(nq, 1)
+        pa, p3, pt, pd, pr = (P(*[x.ctypes.data for x in v]) for v in (qa, q3, ts, ds, res))
+        Ls = np.array([len(x) for x in q3], np.int32)
+        ns = np.array([len(x) for x in ts], np.int32)
+        ident = None if identity is None else np.ascontiguousarray(identity, np.int64)
+        nres = np.full(max(nq, 1), -7, np.int32)
+        rc = lib().fshost_search_rescore_diagonal_batch(self.h, nq, C.cast(pa, C.c_void_p), C.cast(p3, C.c_void_p), _ptr(Ls), _ptr(ident), C.cast(pt, C.c_void_p),
+                                                        C.cast(pd, C.c_void_p), _ptr(ns), C.cast(pr, C.c_void_p), _ptr(nres))
+        self.last_rescore = (res, nres[:nq].copy())
+        if rc != 0:
+            e = FsgpuError(f"rescore_diagonal_batch rc={rc}: {lib().fshost_search_error(self.h).decode()}")
+            e.rc = rc
+            raise e
+        out = [res[i][:nres[i]] for i in range(nq)]
+        bts = [[lib().fshost_search_backtrace(self.h, C.c_void_p(out[i][k:k + 1].ctypes.data)).decode() for k in range(len(out[i]))] for i in range(nq)]
+        return out, bts
+
+    RESCORE_CANARY = 0xA5
 
     def kmer_batch(self, m_kmer, m_ungapped, kmer_thr, spaced, qaa_ptrs, q3_ptrs, lens, pref_identity=None, aln_identity=None, max_res=200, min_diag=30,
                    kmer_score_only=False, rows=None):

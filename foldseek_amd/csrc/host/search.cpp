@@ -1154,13 +1154,17 @@ int fshost_search_rescore_diagonal_batch(fshost_search *s, int nq, const uint8_t
     std::vector<fsgpu_diag_pair> pairs;
     std::vector<size_t> base(nq + 1, 0);
     for (int i = 0; i < nq; i++) {
-        if (!qAA[i] || !q3di[i] || L[i] <= 0 || n[i] < 0) return FSGPU_E_ARG;
+        if (!qAA[i] || !q3di[i] || L[i] <= 0 || n[i] < 0 || (n[i] > 0 && (!targetIds[i] || !diagonals[i] || !results[i]))) {
+            s->err = "fshost_search_rescore_diagonal_batch: query " + std::to_string(i) + ": " +
+                     (!qAA[i] || !q3di[i] ? "null sequence" : L[i] <= 0 ? "length " + std::to_string(L[i]) : n[i] < 0 ? "list length " + std::to_string(n[i]) : "null list");
+            return FSGPU_E_ARG;
+        }
         qLen[i] = L[i];
         qOff[i + 1] = qOff[i] + (uint64_t) ((L[i] + 3) / 4 * 4);
         catA.resize(qOff[i + 1], 20); cat3.resize(qOff[i + 1], 20);
         memcpy(catA.data() + qOff[i], qAA[i], L[i]); memcpy(cat3.data() + qOff[i], q3di[i], L[i]);
         for (int k = 0; k < n[i]; k++) {
-            if (targetIds[i][k] >= s->keys.size()) { s->err = "target id out of range"; return FSGPU_E_ARG; }
+            if (targetIds[i][k] >= s->keys.size()) { s->err = "target id out of range: query " + std::to_string(i) + " entry " + std::to_string(k); return FSGPU_E_ARG; }
             pairs.push_back({(uint32_t) i, targetIds[i][k], (int32_t) diagonals[i][k]});
         }
         base[i + 1] = pairs.size();

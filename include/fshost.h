@@ -172,7 +172,19 @@ int fshost_search_kmer_batch(fshost_search *s, const fshost_matrix *mKmer, const
                              uint32_t *keptIds, int32_t *nkept, fshost_result *results, int32_t *nres, double *seconds);
 /* structurerescorediagonal for nq queries (F/src/strucclustutils/structurerescorediagonal.cpp:50-156,300-370): targetIds / diagonals
  * are the first and third column of the prefilter lines in their order; results[q] has room for n[q] entries; gates, e-value,
- * seq. id, ordering and (with addBacktrace) the all-match backtrace as the module writes them. */
+ * seq. id, ordering and (with addBacktrace) the all-match backtrace as the module writes them.  identityId[q]: the target INDEX that is query q
+ * itself where the module's isIdentity can hold (same database, or --add-self-matches), -1 or identityId == NULL for none; such a hit passes the
+ * criteria whatever they say, but not the coverage and e-value gates in front of them.  L[q] >= 1; n[q] == 0 gives nres[q] == 0 and writes nothing;
+ * nothing is written behind results[q][nres[q]].  A bad argument (null sequence, L[q] <= 0, n[q] < 0, a target id past the database) is FSGPU_E_ARG
+ * with a text that names the query; the handle stays usable.
+ * Two rules here are this library's, not the reference's (held by tests/test_resc_entry_gpu.py):
+ *  - THE SKIP RULE.  A pair whose reference result does not exist -- FSGPU_DIAG_UNDEFINED: negative diagonal, target longer than the query;
+ *    FSGPU_DIAG_NO_OVERLAP: diagonal outside the sequences -- is looked at after Util::canBeCovered, like any pair.  With skipUndefinedDiagonals it is
+ *    passed over and touches NEITHER counter: it is not an accepted hit (maxAccept), not a rejected one (maxRejected), and it does not reset the
+ *    count of rejected hits; the list gives the records it would give with that line deleted.  Without it the call fails with FSGPU_E_UNSUPPORTED
+ *    and a text that names query, target key, diagonal and which of the two cases it was; nres / results of that call are then undefined.
+ *  - AN UNREACHED UNDEFINED PAIR IS NOT AN ERROR.  The test above runs where the accept loop reaches a pair: one that lies behind the cut of maxAccept
+ *    / maxRejected, or whose target cannot be covered, is never an error (an uncoverable one counts as rejected, as every uncoverable target does). */
 int fshost_search_rescore_diagonal_batch(fshost_search *s, int nq, const uint8_t *const *qAA, const uint8_t *const *q3di, const int *L,
                                          const int64_t *identityId, const uint32_t *const *targetIds, const int16_t *const *diagonals,
                                          const int *n, fshost_result *const *results, int *nres);
