@@ -91,6 +91,14 @@ class TmTask(C.Structure):
                 ("d0Search", C.c_float), ("reserved", C.c_uint32)]
 
 
+class TmResult(C.Structure):
+    """fsgpu_tm_result"""
+    _fields_ = [("nPairs", C.c_int32), ("source", C.c_int32), ("score", C.c_float * 2), ("rms", C.c_float), ("t", C.c_float * 3), ("u", C.c_float * 9)]
+
+
+TM_SRC_NONE, TM_SRC_KABSCH, TM_SRC_SEARCH1, TM_SRC_SEARCH2, TM_SRC_EXACT = range(5)          # FSGPU_TM_SRC_*
+
+
 class FsgpuError(RuntimeError):
     pass
 
@@ -119,6 +127,9 @@ def lib():
         "fsgpu_block_backtrace_footprint": (i32, [vp, i32]),
         "fsgpu_lddt_batch": (i32, [vp, C.POINTER(LddtQuery), i32, C.POINTER(LddtTask), i32, vp, u64, vp, u64, vp, vp, u64]),
         "fsgpu_tm_batch": (i32, [vp, C.POINTER(LddtQuery), i32, C.POINTER(TmTask), i32, vp, u64, vp, u64, vp, vp, vp]),
+        "fsgpu_tm_superpose_batch": (i32, [vp, C.POINTER(LddtQuery), i32, C.POINTER(TmTask), i32, vp, u64, vp, u64, i32, C.POINTER(TmResult)]),
+        "fshost_tm_exact_params": (None, [i32, vp]),
+        "fshost_tm_exact_finish": (f64, [i32, f32, f32, vp]),
         "fshost_tm_params": (None, [i32, vp]),
         "fshost_tm_finish": (f64, [i32, f32, f32, i32]),
         "fshost_tm_normalization": (i32, [i32, i32, i32, i32]),
@@ -225,7 +236,7 @@ def exported_symbols():
             "fsgpu_db_adopt_device", "fsgpu_db_check_table", "fsgpu_db_size", "fsgpu_db_residues", "fsgpu_gapless_scan", "fsgpu_gapless_scores",
             "fsgpu_gapless_launch", "fsgpu_gapless_finish", "fsgpu_sw_batch", "fsgpu_sw_multi", "fsgpu_sw_multi_dir", "fsgpu_sw_multi_dir_c", "fsgpu_sw_multi_c", "fsgpu_sw_launch", "fsgpu_sw_finish",
             "fsgpu_db_broadcast", "fsgpu_rccl_selfcheck", "fsgpu_device_count", "fsgpu_live_devices", "fsgpu_gapless_plan_items", "fsgpu_gapless_item_records", "fsgpu_block_backtrace", "fsgpu_block_backtrace_footprint",
-            "fsgpu_lddt_batch", "fsgpu_tm_batch", "fsgpu_last_kernel_ms", "fsgpu_history_counters", "fsgpu_sw_last_passes", "fsgpu_sw3_last_plan", "fsgpu_kmer_index_build", "fsgpu_kmer_index_entries", "fsgpu_kmer_index_entry_bytes", "fsgpu_kmer_index_get_params", "fsgpu_kmer_search",
+            "fsgpu_lddt_batch", "fsgpu_tm_batch", "fsgpu_tm_superpose_batch", "fsgpu_last_kernel_ms", "fsgpu_history_counters", "fsgpu_sw_last_passes", "fsgpu_sw3_last_plan", "fsgpu_kmer_index_build", "fsgpu_kmer_index_entries", "fsgpu_kmer_index_entry_bytes", "fsgpu_kmer_index_get_params", "fsgpu_kmer_search",
             "fsgpu_kmer_index_copy", "fsgpu_kmer_row_copy", "fsgpu_kmer_last_counts", "fsgpu_kmer_last_segments", "fsgpu_kmer_plan_coarse", "fsgpu_kmer_batch_hint",
             "fsgpu_diag_rescore", "fsgpu_sw_batch_seqs"]
 
@@ -793,6 +804,37 @@ class Context:
         self._chk(lib().fsgpu_tm_batch(self.h, qs, nq, ts, nt, _ptr(tc), tc.size, _ptr(bt), bt.size, _ptr(n), _ptr(scores), _ptr(rmsd)), "fsgpu_tm_batch")
         return [(int(n[k]), scores[k], scores[nt + k], rmsd[k]) for k in range(nt)]
 
+    def tm_superpose_batch(self, queries, targets, tasks, exact=False, params=None):
+        """fsgpu_tm_superpose_batch called directly: tm_batch's arguments; exact: the search of --exact-tmscore 1 (the per-task scalars then come from
+        fshost_tm_exact_params).  Returns one dict per task: pairs, scores (float32 [2]; exact: [score_max, -1]), rms (the raw float32), source
+        (TM_SRC_*), t (float32 [3]), u (float32 [3, 3]).  tm_finish / tm_exact_finish turn the raw values into the TM-score and the rmsd."""
+        nq, nt = len(queries), len(tasks)
+        qs, keep = (LddtQuery * max(nq, 1))(), []
+        for i, q in enumerate(queries):
+            q = np.ascontiguousarray(q, np.float32)
+            if q.ndim != 2 or q.shape[0] != 3:
+                raise FsgpuError(f"tm_superpose_batch: query {i}: coordinates must be float32 [3, L]")
+            keep.append(q)
+            qs[i].ca, qs[i].L, qs[i].reserved = q.ctypes.data, q.shape[1], 0
+        tl = [np.ascontiguousarray(t, np.float32) for t in targets]
+        toff = np.concatenate([[0], np.cumsum([t.size for t in tl])]).astype(np.int64)
+        tc = np.concatenate([t.reshape(-1) for t in tl]) if tl else np.zeros(0, np.float32)
+        bts = [str(t[4]).encode() for t in tasks]
+        ts = (TmTask * max(nt, 1))()
+        boff, par = 0, {}
+        for k, (q, t, qs0, ds0, _, norm_len) in enumerate(tasks):
+            ts[k].query, ts[k].tLen, ts[k].tOff, ts[k].qStart, ts[k].dbStart = int(q), tl[int(t)].shape[1], int(toff[int(t)]), int(qs0), int(ds0)
+            ts[k].btOff, ts[k].btLen, ts[k].reserved = boff, len(bts[k]), 0
+            if norm_len not in par:
+                par[norm_len] = tm_exact_params(norm_len) if exact else tm_params(norm_len)
+            ts[k].scoreD8, ts[k].d0Std, ts[k].d0, ts[k].d0Search = (float(v) for v in (params[k] if params is not None else par[norm_len]))
+            boff += len(bts[k])
+        bt = np.frombuffer(b"".join(bts), np.uint8) if boff else np.zeros(0, np.uint8)
+        res = (TmResult * max(nt, 1))()
+        self._chk(lib().fsgpu_tm_superpose_batch(self.h, qs, nq, ts, nt, _ptr(tc), tc.size, _ptr(bt), bt.size, 1 if exact else 0, res), "fsgpu_tm_superpose_batch")
+        return [{"pairs": int(r.nPairs), "source": int(r.source), "scores": np.array(r.score[:], np.float32), "rms": np.float32(r.rms),
+                 "t": np.array(r.t[:], np.float32), "u": np.array(r.u[:], np.float32).reshape(3, 3)} for r in res[:nt]]
+
     def block_backtrace_footprint(self, workgroups_per_cu):
         """workgroups of the block aligner per compute unit for the following block_backtrace calls (0: the default)"""
         self._chk(lib().fsgpu_block_backtrace_footprint(self.h, int(workgroups_per_cu)), "fsgpu_block_backtrace_footprint")
@@ -1118,6 +1160,20 @@ def tm_params(norm_len):
     out = np.zeros(4, np.float32)
     lib().fshost_tm_params(int(norm_len), _ptr(out))
     return out
+
+
+def tm_exact_params(norm_len):
+    """fshost_tm_exact_params: (score_d8, Lnorm, d0, d0_search) of the exact mode for a normalisation length, float32 [4]"""
+    out = np.zeros(4, np.float32)
+    lib().fshost_tm_exact_params(int(norm_len), _ptr(out))
+    return out
+
+
+def tm_exact_finish(pairs, score, raw_rms):
+    """fshost_tm_exact_finish: (TM-score as a double, rmsd as numpy float32) from the raw values of an exact-mode task"""
+    rmsd = np.zeros(1, np.float32)
+    tm = lib().fshost_tm_exact_finish(int(pairs), float(np.float32(score)), float(np.float32(raw_rms)), _ptr(rmsd))
+    return tm, rmsd[0]
 
 
 def tm_finish(pairs, s1, s2, norm_len):

@@ -85,7 +85,7 @@ void fsgpu_destroy(fsgpu_ctx *ctx) {
                       &ctx->img, &ctx->tids, &ctx->res0, &ctx->res1, &ctx->border0, &ctx->border1, &ctx->keys, &ctx->lbuf, &ctx->lres,
                       &ctx->ovAA, &ctx->ovSS, &ctx->ovOff, &ctx->ovLen, &ctx->s3img, &ctx->s3pass, &ctx->s3build, &ctx->s3res,
                       &ctx->btSeq, &ctx->btTrace, &ctx->btBlocks, &ctx->btOut, &ctx->btIn, &ctx->ldIn, &ctx->ldNorm, &ctx->ldCols, &ctx->ldOut,
-                      &ctx->tmIn, &ctx->tmPairs, &ctx->tmMasks, &ctx->tmOut,
+                      &ctx->tmIn, &ctx->tmPairs, &ctx->tmMasks, &ctx->tmOut, &ctx->tmParts,
                       &ctx->mqPssm, &ctx->mqScores, &ctx->mqQueues, &ctx->mqRec, &ctx->mqHist, &ctx->mqBaseGt, &ctx->mqBaseTie, &ctx->mqMeta,
                       &ctx->mqOutId, &ctx->mqOutScore, &ctx->mqIdent};
     for (DevBuf *b : bufs) if (b->p) hipFree(b->p);
@@ -96,6 +96,7 @@ void fsgpu_destroy(fsgpu_ctx *ctx) {
     hipHostFree(ctx->hBtIn.p); hipHostFree(ctx->hBtOut.p); hipHostFree(ctx->hLdIn.p); hipHostFree(ctx->hLdOut.p);
     hipHostFree(ctx->hTmIn.p); hipHostFree(ctx->hTmOut.p);
     for (int i = 0; i < 3; i++) if (ctx->tmEv[i]) (void) hipEventDestroy(ctx->tmEv[i]);
+    for (int i = 0; i < 4; i++) if (ctx->tmSpEv[i]) (void) hipEventDestroy(ctx->tmSpEv[i]);
     for (int i = 0; i < 3; i++) if (ctx->ldEv[i]) (void) hipEventDestroy(ctx->ldEv[i]);
     if (ctx->swLong) (void) hipStreamDestroy(ctx->swLong);
     if (ctx->swHi) (void) hipStreamDestroy(ctx->swHi);
@@ -138,6 +139,7 @@ double fsgpu_last_kernel_ms(const fsgpu_ctx *ctx, int which) {
     if (ctx && which >= 2 && which < 14) return ctx->kmerMs[which - 2];
     if (ctx && (which == 14 || which == 15)) return ctx->ldMs[which - 14];
     if (ctx && (which == 16 || which == 17)) return ctx->tmMs[which - 16];
+    if (ctx && which >= 18 && which <= 20) return ctx->tmSpMs[which - 18];
     if (!ctx || which < 0 || which > 1 || !ctx->evValid[which]) return -1.0;
     if (which == 0 && ctx->mqScanMs >= 0) return ctx->mqScanMs;      // a multi-query call with row-tiled queries: all of its scans
     float ms = 0;

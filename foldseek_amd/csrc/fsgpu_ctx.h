@@ -160,6 +160,10 @@ struct fsgpu_ctx {
     PinBuf hTmIn, hTmOut;
     hipEvent_t tmEv[3] = {nullptr, nullptr, nullptr};
     double tmMs[2] = {-1, -1};
+    // fsgpu_tm_superpose_batch (k_tm_exact.hpp) shares the buffers above; its own: the per-block partials, and its three kernels' times
+    DevBuf tmParts;
+    hipEvent_t tmSpEv[4] = {nullptr, nullptr, nullptr, nullptr};
+    double tmSpMs[3] = {-1, -1, -1};
     std::vector<uint32_t> tmCounts;
     struct {
         bool pending = false;

@@ -140,6 +140,9 @@ const FlagSpec kConvertFlags[] = {             // LocalParameters::convertalignm
     {"--gap-extend", false, IGNORE, nullptr}, {"--db-output", true, USE, "0"}, {"--search-type", false, IGNORE, nullptr},
     {"--exact-tmscore", false, USE, nullptr}, {nullptr, false, USE, nullptr}};          // refused with a TM column, without effect otherwise
 
+const FlagSpec kAln2TmFlags[] = {              // aln2tmscore reads both (aln2tmscore.cpp:67,106); the reference's parameter list for it offers neither (README)
+    {"--tmscore-threshold-mode", false, USE, nullptr}, {"--exact-tmscore", false, USE, nullptr}, {nullptr, false, USE, nullptr}};
+
 const FlagSpec kIndexdbFlags[] = {             // Parameters::indexdb (Parameters.cpp:850-872)
     {"--seed-sub-mat", false, ONLY, "3di.out"}, {"-k", false, ONLY, "0|6"}, {"--alph-size", false, ONLY, "21"},
     {"--comp-bias-corr", false, USE, nullptr}, {"--comp-bias-corr-scale", false, IGNORE, nullptr}, {"--max-seq-len", false, USE, nullptr},
@@ -2461,5 +2464,138 @@ extern "C" int fsmod_convertalis(int argc, const char **argv) {
         ioOk = (fclose(plain) == 0) && ioOk;
         if (!ioOk) return fail("write error on " + o.pos[3]);
     }
+    return EXIT_SUCCESS;
+}
+
+// aln2tmscore (F/src/strucclustutils/aln2tmscore.cpp): for every record of an alignment DB the TM-score and the superposition that reached it, one
+// line `dbKey tmscore t0 t1 t2 u00 u01 .. u22` (SSTR: the score a double "%.3E", t / u floats "%.3f"), the lines of a query under the query's key in a
+// DBTYPE_TMSCORE DB.  All of it comes from fsgpu_tm_superpose_batch, one call per chunk of alignment entries (about 256 KB of records, as the TM
+// columns of convertalis); the entries are written in data-file order, which is what the reference leaves with --threads 1.
+extern "C" int fsmod_aln2tmscore(int argc, const char **argv) {
+    Options o;
+    {
+        std::string perr;
+        if (!parseArgs(argc, argv, "aln2tmscore", {kAln2TmFlags, kCommonFlags}, o, perr)) return fail(perr);
+    }
+    if (o.pos.size() != 4) return fail("usage: aln2tmscore <queryDB> <targetDB> <alignmentDB> <outDB> [--tmscore-threshold-mode 0|1|2] [--exact-tmscore 0|1]");
+    const int mode = o.geti("--tmscore-threshold-mode", 0), exact = o.geti("--exact-tmscore", 0);
+    if (mode < 0 || mode > 2) return fail("aln2tmscore: --tmscore-threshold-mode " + std::to_string(mode) + " is not one of 0 (alignment), 1 (query), 2 (target)");
+    if (exact != 0 && exact != 1) return fail("aln2tmscore: --exact-tmscore takes 0 or 1");
+    if (o.has("--gpus") && o.kv["--gpus"] != "1") return fail("aln2tmscore: --gpus " + o.kv["--gpus"] + " is not implemented for this module (one device: --gpu-device)");
+    const bool sameDB = o.pos[0] == o.pos[1];
+    for (int k = 0; k < (sameDB ? 1 : 2); k++)
+        if (!DbReader::caExists(o.pos[k])) return fail("aln2tmscore: " + o.pos[k] + " has no C-alpha coordinates (no <db>_ca)");
+    std::string err;
+    DbReader qSeq, tSeqOwn, qCa, tCaOwn, aln;
+    if (!qSeq.open(o.pos[0], err) || (!sameDB && !tSeqOwn.open(o.pos[1], err))) return fail(err);
+    if (!qCa.openCa(o.pos[0], err) || (!sameDB && !tCaOwn.openCa(o.pos[1], err))) return fail(err);
+    if (!aln.open(o.pos[2], err)) return fail(err);
+    const DbReader &tSeq = sameDB ? qSeq : tSeqOwn, &tCa = sameDB ? qCa : tCaOwn;
+    std::vector<size_t> order(aln.size());
+    for (size_t i = 0; i < order.size(); i++) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return aln.offset(a) < aln.offset(b); });
+
+    // ---- pass over one chunk: parse and check every record (nothing has touched a device yet when a record is refused in the first chunk)
+    struct Rec { uint32_t dbKey; int normLen; };
+    std::vector<Rec> recs;
+    std::vector<size_t> recsOfEntry;
+    std::vector<std::vector<float>> qCoords;
+    std::vector<fsgpu_lddt_query> queries;
+    std::vector<fsgpu_tm_task> tasks;
+    std::vector<fsgpu_tm_result> results;
+    std::vector<float> tCoords;
+    std::map<std::pair<uint32_t, int>, uint64_t> tWhere;
+    std::string bts, bt, text;
+    fsgpu_ctx *ctx = nullptr;
+    struct CtxGuard { fsgpu_ctx *&c; ~CtxGuard() { if (c) fsgpu_destroy(c); } } guard{ctx};
+    DbWriter w;
+    bool opened = false;
+    for (size_t oi = 0; oi < order.size();) {
+        size_t end = oi, bytes = 0;
+        while (end < order.size() && (end == oi || bytes + aln.entryLen(order[end]) <= ((size_t) 256 << 10))) bytes += aln.entryLen(order[end++]);
+        recs.clear(); recsOfEntry.clear(); qCoords.clear(); tasks.clear(); tCoords.clear(); tWhere.clear(); bts.clear();
+        for (size_t e = oi; e < end; e++) {
+            const size_t i = order[e];
+            const uint32_t queryKey = aln.key(i);
+            const char *data = aln.data(i), *dataEnd = data + aln.entryLen(i);
+            size_t nRec = 0;
+            int Lq = 0;
+            bool haveQuery = false;
+            while (data < dataEnd && *data != '\0') {
+                if (!haveQuery) {
+                    const int64_t qs = qSeq.idOf(queryKey), qc = qCa.idOf(queryKey);
+                    if (qs < 0 || qc < 0) return fail("aln2tmscore: query key " + std::to_string(queryKey) + " has no sequence or no C-alpha entry");
+                    Lq = (int) qSeq.seqLen((size_t) qs);
+                    qCoords.emplace_back(3 * (size_t) std::max(Lq, 1));
+                    if (Lq <= 0 || fshost_ca_decode(qCa.data((size_t) qc), qCa.entryLen((size_t) qc), Lq, qCoords.back().data()) != 0)
+                        return fail("aln2tmscore: the C-alpha entry of query " + std::to_string(queryKey) + " is shorter than its sequence needs");
+                    haveQuery = true;
+                }
+                const char *lineEnd = data;
+                while (lineEnd < dataEnd && *lineEnd != '\n' && *lineEnd != '\0') lineEnd++;
+                AlnRecord res;
+                if (!parseAlnRecord(data, lineEnd, res, err)) return fail(err);
+                data = (lineEnd < dataEnd && *lineEnd == '\n') ? lineEnd + 1 : lineEnd;
+                if (res.backtrace.empty())
+                    return fail("Backtrace cigar is missing in the alignment result. Please recompute the alignment with the -a flag.\nCommand: foldseek structurealign " +
+                                o.pos[0] + " " + o.pos[1] + " " + o.pos[2] + " alnNew -a");
+                const int64_t ts = tSeq.idOf(res.dbKey), tc = tCa.idOf(res.dbKey);
+                if (ts < 0 || tc < 0) return fail("aln2tmscore: target key " + std::to_string(res.dbKey) + " has no sequence or no C-alpha entry");
+                const int Lt = (int) tSeq.seqLen((size_t) ts);
+                if (Lt <= 0 || !expandBacktrace(res.backtrace, (size_t) Lq + (size_t) Lt + 1, bt))
+                    return fail("aln2tmscore: the alignment of query " + std::to_string(queryKey) + " with target " + std::to_string(res.dbKey) + " does not fit the databases");
+                if (bt.find('M') == std::string::npos)
+                    return fail("aln2tmscore: the alignment of query " + std::to_string(queryKey) + " with target " + std::to_string(res.dbKey) +
+                                " has no M column: the reference prints an uninitialised superposition for it");
+                auto it = tWhere.find({res.dbKey, Lt});
+                if (it == tWhere.end()) {
+                    const size_t at = tCoords.size();
+                    tCoords.resize(at + 3 * (size_t) Lt);
+                    if (fshost_ca_decode(tCa.data((size_t) tc), tCa.entryLen((size_t) tc), Lt, tCoords.data() + at) != 0)
+                        return fail("aln2tmscore: target key " + std::to_string(res.dbKey) + " has no C-alpha entry of " + std::to_string(Lt) + " residues");
+                    it = tWhere.emplace(std::make_pair(res.dbKey, Lt), (uint64_t) at).first;
+                }
+                const int normLen = fshost_tm_normalization(mode, std::min(res.qEnd - res.qStart, res.dbEnd - res.dbStart), res.qLen, res.dbLen);
+                fsgpu_tm_task k;
+                k.query = (uint32_t) (qCoords.size() - 1); k.tLen = Lt; k.tOff = it->second; k.qStart = res.qStart; k.dbStart = res.dbStart;
+                k.btOff = bts.size(); k.btLen = (uint32_t) bt.size(); k.reserved = 0;
+                float par[4];
+                if (exact) fshost_tm_exact_params(normLen, par); else fshost_tm_params(normLen, par);
+                k.scoreD8 = par[0]; k.d0Std = par[1]; k.d0 = par[2]; k.d0Search = par[3];
+                bts += bt;
+                tasks.push_back(k);
+                recs.push_back({res.dbKey, normLen});
+                nRec++;
+            }
+            recsOfEntry.push_back(nRec);
+        }
+        if (!tasks.empty()) {
+            if (!ctx && fsgpu_create(o.geti("--gpu-device", 0), &ctx) != FSGPU_OK) return fail(std::string("GPU: ") + fsgpu_last_error(nullptr));
+            queries.resize(qCoords.size());
+            for (size_t i = 0; i < qCoords.size(); i++) { queries[i].ca = qCoords[i].data(); queries[i].L = (int32_t) (qCoords[i].size() / 3); queries[i].reserved = 0; }
+            results.resize(tasks.size());
+            if (fsgpu_tm_superpose_batch(ctx, queries.data(), (int) queries.size(), tasks.data(), (int) tasks.size(), tCoords.data(), tCoords.size(), bts.data(),
+                                         bts.size(), exact, results.data()) != FSGPU_OK) return fail(std::string("aln2tmscore: ") + fsgpu_last_error(ctx));
+        }
+        if (!opened) { if (!w.open(o.pos[3], 102 /* LocalParameters::DBTYPE_TMSCORE */, err)) return fail(err); opened = true; }
+        size_t r = 0;
+        for (size_t e = oi; e < end; e++) {
+            text.clear();
+            for (size_t k = 0; k < recsOfEntry[e - oi]; k++, r++) {
+                const fsgpu_tm_result &g = results[r];
+                const double tm = exact ? fshost_tm_exact_finish(g.nPairs, g.score[0], g.rms, nullptr) : fshost_tm_finish(g.nPairs, g.score[0], g.score[1], recs[r].normLen);
+                text += std::to_string(recs[r].dbKey);
+                text.push_back(' ');
+                appendE3(text, tm);
+                for (int c = 0; c < 3; c++) { text.push_back(' '); appendF3(text, g.t[c]); }
+                for (int c = 0; c < 9; c++) { text.push_back(' '); appendF3(text, g.u[c]); }
+                text.push_back('\n');
+            }
+            w.write(aln.key(order[e]), text.data(), text.size());
+        }
+        oi = end;
+    }
+    if (!opened && !w.open(o.pos[3], 102, err)) return fail(err);
+    if (!w.close(err)) return fail(err);
     return EXIT_SUCCESS;
 }

@@ -40,6 +40,34 @@ double fshost_tm_finish(int nPairs, float s1, float s2, int normLen) {
     return (b < a) ? a : b;                                       // std::max(TM, TMalnScore)
 }
 
+// The exact mode (computeExactTMscore, TMaligner.cpp:107-202): score_d8 from parameter_set4search(normLen, normLen), Lnorm / d0 / d0_search from
+// parameter_set4final((float) normLen) -- the four floats of a fsgpu_tm_task in that order, Lnorm in the d0Std field.
+void fshost_tm_exact_params(int normLen, float out[4]) {
+    const float Lnorm = (float) normLen;
+    volatile double p8 = pow(Lnorm * 1.0, 0.3);
+    volatile double m8 = 1.5 * p8;
+    out[0] = (float) (m8 + 3.5);
+    out[1] = Lnorm;
+    volatile float d0;
+    if (Lnorm <= 21) d0 = 0.5f;
+    else { volatile double p = pow(Lnorm * 1.0 - 15, 1.0 / 3); volatile double m = 1.24 * p; d0 = (float) (m - 1.8); }
+    if (d0 < 0.5f) d0 = 0.5f;
+    out[2] = d0;
+    float d0Search = d0;
+    if (d0Search > 8) d0Search = 8;
+    if (d0Search < 4.5) d0Search = 4.5;
+    out[3] = d0Search;
+}
+
+// TM = (double) score_max; rmsd0 = sqrt(rmsd0 / n_ali8): a float divided by an int, the root taken of that float and stored in a float again
+double fshost_tm_exact_finish(int nPairs, float score, float rawRms, float *rmsd) {
+    if (rmsd) {
+        volatile float q = rawRms / (float) nPairs;
+        *rmsd = (float) sqrt((double) q);
+    }
+    return (double) score;
+}
+
 int fshost_tm_normalization(int mode, int alignmentLen, int queryLen, int targetLen) {
     switch (mode) {
         case 0: return alignmentLen;

@@ -439,14 +439,14 @@ TM_HD uint32_t tmScorePass(const TmView &v, const float t[3], const float u[3][3
     return nCut;
 }
 
-// score_fun8 (Lnorm = n) after do_rotation.  The relief loop (`n_cut < 3 && n_ali > 3`: d_tmp = (float) ((d + inc * 0.5)^2), inc = 1, 2, ...) is solved
+// score_fun8 after do_rotation; `div` is its Lnorm (n in the approximate searches, the normalisation length in the exact one).  The relief loop (`n_cut < 3 && n_ali > 3`: d_tmp = (float) ((d + inc * 0.5)^2), inc = 1, 2, ...) is solved
 // for the first inc whose threshold exceeds the third smallest di instead of being walked; the selection of that inc is what the reference ends with.
 // Returns false where the reference's loop would never end (fewer than three pairs with a finite distance): the caller leaves the start.
-TM_HD bool tmScoreFun8(const TmView &v, const float t[3], const float u[3][3], float d, float scoreD8, float d0, uint32_t *mout, uint32_t &nCut, float &score) {
+TM_HD bool tmScoreFun8(const TmView &v, const float t[3], const float u[3][3], float d, float scoreD8, float d0, float div, uint32_t *mout, uint32_t &nCut, float &score) {
     const float d02 = d0 * d0, cut = scoreD8 * scoreD8;
     float dTmp = d * d, sum, low[3];
     nCut = tmScorePass(v, t, u, dTmp, cut, d02, mout, sum, low);
-    score = sum / (float) v.n;
+    score = sum / div;
     if (nCut < 3 && v.n > 3) {
         if (!(low[2] < __builtin_inff())) return false;
         const double dd = (double) d, third = (double) low[2];
@@ -469,8 +469,28 @@ TM_HD bool tmScoreFun8(const TmView &v, const float t[3], const float u[3][3], f
     return true;
 }
 
-// one fragment start of TMscore8_search_standard: the body of its `while (1)`; returns the largest score seen (at least `best`)
-TM_HD float tmStart(const TmView &v, uint32_t start, uint32_t len, float d0Search, float scoreD8, float d0, float best) {
+// a lane's best score with the superposition that first reached it: the reference overwrites t0 / u0 at every STRICT improvement of score_max, so what
+// is left is the rotation at the first occurrence of the maximum in its serial order (fragment length, start, refinement round).  ord: the ordinal of
+// the fragment start in that order; kTmNoOrd while score_max still has its initial -1.
+constexpr uint32_t kTmNoOrd = 0xffffffffu;
+struct TmBest {
+    float score;
+    uint32_t ord;
+    float t[3], u[3][3];
+};
+
+TM_HD void tmTake(TmBest &b, float score, uint32_t ord, const float t[3], const float u[3][3]) {
+    b.score = score; b.ord = ord;
+    for (int i = 0; i < 3; i++) {
+        b.t[i] = t[i];
+        for (int j = 0; j < 3; j++) b.u[i][j] = u[i][j];
+    }
+}
+
+// one fragment start of TMscore8_search_standard (rounds = 20, div = n) or of TMscore8_search (rounds = 10, div = Lnorm): the body of its `while (1)`.
+// Returns the largest score seen (at least `best`); with kTrack, *tb (whose score is `best`) follows every strict improvement.
+template <bool kTrack>
+TM_HD float tmStartT(const TmView &v, uint32_t start, uint32_t len, float d0Search, float scoreD8, float d0, float div, int rounds, float best, TmBest *tb, uint32_t ord) {
     uint32_t *cur = v.m[0], *nxt = v.m[1];
     for (uint32_t w = 0; w < v.words; w++) {
         const uint32_t lo = w * 32, hi = lo + 32;
@@ -484,15 +504,15 @@ TM_HD float tmStart(const TmView &v, uint32_t start, uint32_t len, float d0Searc
     float rms, t[3], u[3][3], score;
     uint32_t nCut;
     tmKabschFast(v, cur, len, rms, t, u);
-    if (!tmScoreFun8(v, t, u, d0Search - 1.0f, scoreD8, d0, nxt, nCut, score)) return best;
-    if (score > best) best = score;
+    if (!tmScoreFun8(v, t, u, d0Search - 1.0f, scoreD8, d0, div, nxt, nCut, score)) return best;
+    if (score > best) { best = score; if (kTrack) tmTake(*tb, score, ord, t, u); }
     const float d = d0Search + 1.0f;
-    for (int it = 0; it < kTmRounds; it++) {
+    for (int it = 0; it < rounds; it++) {
         uint32_t *s = cur; cur = nxt; nxt = s;
         const uint32_t ka = nCut;
         tmKabschFast(v, cur, ka, rms, t, u);
-        if (!tmScoreFun8(v, t, u, d, scoreD8, d0, nxt, nCut, score)) return best;
-        if (score > best) best = score;
+        if (!tmScoreFun8(v, t, u, d, scoreD8, d0, div, nxt, nCut, score)) return best;
+        if (score > best) { best = score; if (kTrack) tmTake(*tb, score, ord, t, u); }
         if (nCut == ka) {
             bool same = true;
             for (uint32_t w = 0; w < v.words; w++) same &= cur[(size_t) w * v.ms] == nxt[(size_t) w * v.ms];
@@ -502,8 +522,13 @@ TM_HD float tmStart(const TmView &v, uint32_t start, uint32_t len, float d0Searc
     return best;
 }
 
-// fragment lengths n, n/2, n/4 ... down to min(4, n), at most 6; returns their number.  starts[k]: fragment starts of length k (0, 40, 80 ..., last forced)
-TM_HD int tmFragments(uint32_t n, uint32_t len[6], uint32_t starts[6]) {
+TM_HD float tmStart(const TmView &v, uint32_t start, uint32_t len, float d0Search, float scoreD8, float d0, float best) {
+    return tmStartT<false>(v, start, len, d0Search, scoreD8, d0, (float) v.n, kTmRounds, best, nullptr, 0u);
+}
+
+// fragment lengths n, n/2, n/4 ... down to min(4, n), at most 6; returns their number.  starts[k]: fragment starts of length k (0, step, 2 step ...,
+// last forced)
+TM_HD int tmFragments(uint32_t n, uint32_t len[6], uint32_t starts[6], uint32_t step = kTmStep) {
     const uint32_t lmin = n < 4u ? n : 4u;
     int cnt = 0, i;
     for (i = 0; i < 5; i++) {
@@ -514,17 +539,17 @@ TM_HD int tmFragments(uint32_t n, uint32_t len[6], uint32_t starts[6]) {
     if (i == 5) { cnt++; len[5] = lmin; }
     for (int k = 0; k < cnt; k++) {
         const uint32_t imax = n - len[k];
-        starts[k] = imax == 0 ? 1u : (imax + kTmStep - 1) / kTmStep + 1u;
+        starts[k] = imax == 0 ? 1u : (imax + step - 1) / step + 1u;
     }
     return cnt;
 }
 
 // the s-th start over all fragment lengths -> (start, length)
-TM_HD void tmNthStart(uint32_t n, int cnt, const uint32_t len[6], const uint32_t starts[6], uint32_t s, uint32_t &start, uint32_t &flen) {
+TM_HD void tmNthStart(uint32_t n, int cnt, const uint32_t len[6], const uint32_t starts[6], uint32_t s, uint32_t &start, uint32_t &flen, uint32_t step = kTmStep) {
     int k = 0;
     while (k < cnt - 1 && s >= starts[k]) { s -= starts[k]; k++; }
     flen = len[k];
-    const uint32_t imax = n - flen, pos = s * kTmStep;
+    const uint32_t imax = n - flen, pos = s * step;
     start = pos < imax ? pos : imax;
 }
 

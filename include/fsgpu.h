@@ -26,6 +26,7 @@
  *   fsgpu_sw_multi / _multi_dir       the same for a batch of queries, one device launch per register class and direction
  *                                     (forward over all pairs, reversed over the pairs alignStructure still needs:
  *                                     F/src/strucclustutils/structurealign.cpp:50-65)
+ *   fsgpu_tm_superpose_batch          TMaligner::computeTMscore (both modes) with t / u                  F/src/commons/TMaligner.cpp:50-212
  *   fsgpu_tm_batch                    TMaligner::computeAppoximateTMscore                               F/src/commons/TMaligner.cpp:50-104, F/lib/tmalign
  *   fsgpu_lddt_batch                  LDDTCalculator::initQuery / computeLDDTScore                      F/src/commons/LDDT.cpp:87-215, call sites
  *                                     F/src/strucclustutils/structurealign.cpp:331-341,398-408, structureconvertalis.cpp:770-773
@@ -341,7 +342,7 @@ int fsgpu_lddt_batch(fsgpu_ctx *ctx, const fsgpu_lddt_query *queries, int nq, co
  * rmsd[k].  All of it bit for bit what the reference computes, except where the double-precision atan2 / cos / sin of the device library differ from
  * the host's in the last place AND the difference survives the cast to float.  The scalars that need pow() and the final scalings are the
  * host's, with the C library the reference uses: fshost_tm_params fills the five floats of a task from its normalisation length, fshost_tm_finish
- * turns the raw values into the TM-score.  The rotation and translation are not returned.
+ * turns the raw values into the TM-score.  fsgpu_tm_batch does not return the rotation and translation; fsgpu_tm_superpose_batch (below) does.
  * Queries, tCoords, bt and the task geometry as for fsgpu_lddt_batch.  Alignments of any length up to FSGPU_MAX_SEQ_LEN run on the device; there is no
  * host path. */
 typedef struct {
@@ -359,6 +360,37 @@ typedef struct {
 } fsgpu_tm_task;
 int fsgpu_tm_batch(fsgpu_ctx *ctx, const fsgpu_lddt_query *queries, int nq, const fsgpu_tm_task *tasks, int nt, const float *tCoords, uint64_t tCoordsLen,
                    const char *bt, uint64_t btBytes, int32_t *nPairs, float *scores, float *rmsd);
+
+/* ---- TM-score with its superposition, approximate or exact (TMaligner::computeTMscore, F/src/commons/TMaligner.cpp:50-212) ------------------------------
+ * Same arguments and checks as fsgpu_tm_batch.  One record per task; t / u are the translation and rotation the reference's TMscoreResult carries
+ * (x' = t + u x moves the TARGET's residues onto the query's), i.e. the superposition at the FIRST occurrence of the winning search's maximum in the
+ * reference's serial order (fragment length, fragment start, refinement round), whichever workgroup found it.
+ *   exact == 0  computeAppoximateTMscore: score[0] / score[1] = score_max of standard_TMscore's / detailed_search_standard's search, rms = the raw
+ *               rmsd, all three bit for bit what fsgpu_tm_batch returns; fshost_tm_finish as before.  t / u: the second search's, or the first one's
+ *               if the second never beat its initial -1, or the all-pairs KabschFast's if neither did.
+ *   exact == 1  computeExactTMscore: TMscore8_search over all pairs with simplify_step 1 (every fragment start), n_it 10, score_fun8 dividing by
+ *               Lnorm.  The task's four floats are fshost_tm_exact_params' in order: scoreD8, Lnorm IN THE d0Std FIELD (>= 0; 0 gives INF / NaN scores as
+ *               the reference's), d0, d0Search (parameter_set4final).  score[0] = score_max (the TM-score is (double) score[0]), score[1] = -1,
+ *               rms = the raw rms of the all-pairs KabschFast (fshost_tm_exact_finish: sqrt(rms / nPairs)).  t / u: the search's, else the all-pairs
+ *               KabschFast's.  The search spans ceil(starts / 128) workgroups per task; their partials are reduced on the device: larger score, then
+ *               smaller start ordinal, NaN never -- no atomics, nothing depends on the launch order.
+ * A task without 'M' columns: scores -1, rms 0, source FSGPU_TM_SRC_NONE, t = 0, u = identity (nothing runs for it).
+ * The double atan2 / cos / sin caveat of fsgpu_tm_batch applies to every field. */
+#define FSGPU_TM_SRC_NONE 0      /* no pairs */
+#define FSGPU_TM_SRC_KABSCH 1    /* KabschFast over all pairs */
+#define FSGPU_TM_SRC_SEARCH1 2   /* standard_TMscore's search */
+#define FSGPU_TM_SRC_SEARCH2 3   /* detailed_search_standard's search */
+#define FSGPU_TM_SRC_EXACT 4     /* TMscore8_search of the exact mode */
+typedef struct {
+    int32_t nPairs;
+    int32_t source;         /* FSGPU_TM_SRC_*: where t / u came from */
+    float score[2];
+    float rms;
+    float t[3];
+    float u[9];             /* u[3 * i + j] = u[i][j] */
+} fsgpu_tm_result;
+int fsgpu_tm_superpose_batch(fsgpu_ctx *ctx, const fsgpu_lddt_query *queries, int nq, const fsgpu_tm_task *tasks, int nt, const float *tCoords,
+                             uint64_t tCoordsLen, const char *bt, uint64_t btBytes, int exact, fsgpu_tm_result *out);
 
 /* ---- prefilter: k-mer matching with double-diagonal hits + ungapped diagonal scoring ------------------------- */
 /* Index parameters == the subset of Prefiltering's members that shape IndexTable / SequenceLookup.  Sequence-
@@ -468,7 +500,8 @@ int fsgpu_kmer_plan_coarse(const int32_t *lengths, uint64_t n, uint32_t blocksPe
  * 3..10 its stages (similar-k-mer count, index probes, hit gather, partition into (query, bin) segments, double-diagonal
  * detection per segment, scoring, replay, selection), 11 host tail, 12 the index-probe kernel (k_kmer_lists) alone,
  * 14 / 15 the two kernels of the last fsgpu_lddt_batch (k_lddt_norm, k_lddt_pairs),
- * 16 / 17 the two kernels of the last fsgpu_tm_batch (k_tm_pairs, k_tm_search).
+ * 16 / 17 the two kernels of the last fsgpu_tm_batch (k_tm_pairs, k_tm_search),
+ * 18 / 19 / 20 the three kernels of the last fsgpu_tm_superpose_batch (k_tm_pairs, k_tm_sp_search, k_tm_sp_finish).
  * Returns < 0 if nothing was recorded. */
 double fsgpu_last_kernel_ms(const fsgpu_ctx *ctx, int which);
 /* Read-only record of the choices a context makes from what it ran before (for tests; nothing reads it back): out8[0] / [1] the form the count pass

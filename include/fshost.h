@@ -244,6 +244,12 @@ double fshost_lddt_average(const float *cols, int alignLength, int *scoreLength)
  * standard_TMscore's search and s2 of detailed_search_standard's (TMalign.cpp:1423,622; TMaligner.cpp:102).
  * fshost_tm_normalization: TMaligner::normalization(mode, alignmentLen, queryLen, targetLen), mode 0 alignment, 1 query, 2 target; 0 for any other mode. */
 void fshost_tm_params(int normLen, float out[4]);
+/* The exact mode (fsgpu_tm_superpose_batch with exact = 1; computeExactTMscore, F/src/commons/TMaligner.cpp:107-202).
+ * fshost_tm_exact_params: out[0] score_d8 of parameter_set4search(normLen, normLen); out[1] Lnorm, out[2] d0, out[3] d0_search of
+ * parameter_set4final((float) normLen): the four floats of a fsgpu_tm_task in order (Lnorm goes into its d0Std field).
+ * fshost_tm_exact_finish: returns the TM-score (double) score; *rmsd = sqrt(rawRms / nPairs) in float (NaN without pairs). */
+void fshost_tm_exact_params(int normLen, float out[4]);
+double fshost_tm_exact_finish(int nPairs, float score, float rawRms, float *rmsd);
 double fshost_tm_finish(int nPairs, float s1, float s2, int normLen);
 int fshost_tm_normalization(int mode, int alignmentLen, int queryLen, int targetLen);
 /* Binds C-alpha data and --lddt-threshold to a search handle (structurealign.cpp:177-250,331-341,376-411): with lddtThr > 0 every hit that passes
@@ -284,6 +290,9 @@ int fsmod_structurerescorediagonal(int argc, const char **argv);
  * (--format-mode 0 / 2 / 4) with every --format-output column that is a function of the alignment record, the sequences and the
  * headers (+ the set columns from <db>.lookup / <db>.source); columns that need C-alpha coordinates, taxonomy or multimer data are refused by name.  Host only (text formatting). */
 int fsmod_convertalis(int argc, const char **argv);
+/* aln2tmscore <queryDB> <targetDB> <alnDB> <outDB> (F/src/strucclustutils/aln2tmscore.cpp): per alignment `dbKey tmscore t0 t1 t2 u00 .. u22`, a
+ * DBTYPE_TMSCORE result DB keyed by query.  [--tmscore-threshold-mode 0|1|2] [--exact-tmscore 0|1]; one device. */
+int fsmod_aln2tmscore(int argc, const char **argv);
 /* gpuserver <targetDB_ss[_pad]>: keeps the target DB resident in HBM and serves gapless scans over the reference's
  * shared-memory protocol until SIGINT/SIGTERM (M/src/util/gpuserver.cpp:24-101, M/src/commons/GpuUtil.h:9-49);
  * `ungappedprefilter ... --gpu-server 1` is the client (M/src/prefiltering/ungappedprefilter.cpp:71-122,208-257). */
