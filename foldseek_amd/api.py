@@ -99,6 +99,10 @@ class TmResult(C.Structure):
 TM_SRC_NONE, TM_SRC_KABSCH, TM_SRC_SEARCH1, TM_SRC_SEARCH2, TM_SRC_EXACT = range(5)          # FSGPU_TM_SRC_*
 
 
+FSGPU_E_ARG, FSGPU_E_HIP, FSGPU_E_NODB, FSGPU_E_UNSUPPORTED, FSGPU_E_NOMEM, FSGPU_E_OUTPUT = -1, -2, -3, -4, -5, -6
+SCAN_GUARD = 0xA5A5A5A5          # what Context.sw_scan_c fills its output buffers with before the call
+
+
 class FsgpuError(RuntimeError):
     pass
 
@@ -197,10 +201,14 @@ def lib():
         "fshost_search_prefilter": (i32, [vp, vp, i32, i64, vp]),
         "fshost_search_align": (i32, [vp, vp, vp, i32, i64, vp, i32, vp]),
         "fshost_search_align_batch": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "fshost_search_exhaustive_batch": (i32, [vp, i32, vp, vp, vp, vp, vp, vp]),
+        "fshost_search_exhaustive_survivors": (i32, [vp, vp, i32]),
         "fsgpu_sw_multi": (i32, [vp, vp, i32, i32, i32, vp, vp]),
         "fsgpu_sw_multi_dir": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp]),
         "fsgpu_sw_multi_dir_c": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
         "fsgpu_sw_multi_c": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp]),
+        "fsgpu_sw_scan_c": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, u64, vp]),
+        "fsgpu_sw_scan_last": (None, [vp, vp]),
         "fshost_search_backtrace": (C.c_char_p, [vp, vp]),
         "fshost_search_stats": (None, [vp, vp]),
         "fshost_search_backtrace_counts": (None, [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
@@ -238,7 +246,7 @@ def exported_symbols():
             "fsgpu_db_broadcast", "fsgpu_rccl_selfcheck", "fsgpu_device_count", "fsgpu_live_devices", "fsgpu_gapless_plan_items", "fsgpu_gapless_item_records", "fsgpu_block_backtrace", "fsgpu_block_backtrace_footprint",
             "fsgpu_lddt_batch", "fsgpu_tm_batch", "fsgpu_tm_superpose_batch", "fsgpu_last_kernel_ms", "fsgpu_history_counters", "fsgpu_sw_last_passes", "fsgpu_sw3_last_plan", "fsgpu_kmer_index_build", "fsgpu_kmer_index_entries", "fsgpu_kmer_index_entry_bytes", "fsgpu_kmer_index_get_params", "fsgpu_kmer_search",
             "fsgpu_kmer_index_copy", "fsgpu_kmer_row_copy", "fsgpu_kmer_last_counts", "fsgpu_kmer_last_segments", "fsgpu_kmer_plan_coarse", "fsgpu_kmer_batch_hint",
-            "fsgpu_diag_rescore", "fsgpu_sw_batch_seqs"]
+            "fsgpu_diag_rescore", "fsgpu_sw_batch_seqs", "fsgpu_sw_scan_c", "fsgpu_sw_scan_last"]
 
 
 def _ptr(a):
@@ -639,6 +647,55 @@ class Context:
             rf.append(fwd[b:b + len(k[0])].copy()); rr.append(rev[b:b + len(k[0])].copy()); b += len(k[0])
         return rf, rr
 
+    def sw_scan_c(self, mat3di, matAA, queries, cutoffs, gap_open=10, gap_extend=1, cap=None):
+        """Whole-database forward pass with the selection on the device (fsgpu_sw_scan_c).  queries: tuples as for sw_multi_dir_c without the
+        target ids (a seventh element is ignored); cutoffs: one score per query.  Returns [(ids, records)] per query: ascending target ids and the
+        forward records of the pairs with score >= cutoff.  cap None: the buffers start at 4096 records and the call is repeated once with the
+        size FSGPU_E_OUTPUT reported.  cap given: one call with buffers of cap records followed by one guard record, kept with the base array
+        and the status as last_scan = (rc, base, ids, records); FSGPU_E_OUTPUT then raises FsgpuError with .rc == FSGPU_E_OUTPUT."""
+        class Q(C.Structure):
+            _fields_ = [("qAA", C.c_void_p), ("q3Di", C.c_void_p), ("cbAA_fwd", C.c_void_p), ("cb3Di_fwd", C.c_void_p), ("cbAA_rev", C.c_void_p),
+                        ("cb3Di_rev", C.c_void_p), ("L", C.c_int32), ("n", C.c_int32), ("targetIds", C.c_void_p)]
+        nq = len(queries)
+        m3 = np.ascontiguousarray(mat3di, np.int8)
+        mA = None if matAA is None else np.ascontiguousarray(matAA, np.int8)
+        keep, arr = [], (Q * max(nq, 1))()
+        for i, qt in enumerate(queries):
+            qa, q3, cbaf, cb3f, cbar, cb3r = qt[:6]
+            q3 = np.ascontiguousarray(q3, np.uint8)
+            qa = None if qa is None else np.ascontiguousarray(qa, np.uint8)
+            cbs = [None if x is None else np.ascontiguousarray(x, np.int8) for x in (cbaf, cb3f, cbar, cb3r)]
+            keep.append((q3, qa, cbs))
+            arr[i].qAA, arr[i].q3Di = (None if qa is None else qa.ctypes.data), q3.ctypes.data
+            arr[i].cbAA_fwd, arr[i].cb3Di_fwd, arr[i].cbAA_rev, arr[i].cb3Di_rev = [None if b is None else b.ctypes.data for b in cbs]
+            arr[i].L, arr[i].n, arr[i].targetIds = len(q3), 0, None
+        cut = np.ascontiguousarray(cutoffs, np.int32)
+        if len(cut) != nq:
+            raise ValueError("one cutoff per query")
+        base = np.zeros(nq + 1, np.uint64)
+
+        def call(room):
+            ids = np.full(room + 1, SCAN_GUARD, np.uint32)
+            recs = np.full(room + 1, SCAN_GUARD, np.uint32).repeat(4).view(SWRES_DT)
+            rc = lib().fsgpu_sw_scan_c(self.h, m3.ctypes.data, None if mA is None else mA.ctypes.data, C.cast(arr, C.c_void_p), nq, gap_open, gap_extend,
+                                       _ptr(cut), _ptr(ids), _ptr(recs), room, _ptr(base))
+            return rc, ids, recs
+        rc, ids, recs = call(4096 if cap is None else int(cap))
+        if cap is None and rc == FSGPU_E_OUTPUT:
+            rc, ids, recs = call(int(base[nq]))
+        self.last_scan = (rc, base.copy(), ids, recs)
+        if rc != 0:
+            e = FsgpuError(f"fsgpu_sw_scan_c rc={rc}: {lib().fsgpu_last_error(self.h).decode()}")
+            e.rc = rc
+            raise e
+        return [(ids[int(base[i]):int(base[i + 1])].copy(), recs[int(base[i]):int(base[i + 1])].copy()) for i in range(nq)]
+
+    def sw_scan_last(self):
+        """fsgpu_sw_scan_last: sub-batches, records handed to the host, host ms spent planning, survivors, host ms of the whole call"""
+        o = np.zeros(8)
+        lib().fsgpu_sw_scan_last(self.h, _ptr(o))
+        return {"sub_batches": int(o[0]), "device_selected": int(o[1]), "plan_ms": float(o[2]), "survivors": int(o[3]), "call_ms": float(o[4])}
+
     def sw_batch(self, pAAf, p3f, pAAr, p3r, target_ids, gap_open=10, gap_extend=1):
         p3f = np.ascontiguousarray(p3f, np.int16)
         p3r = np.ascontiguousarray(p3r, np.int16)
@@ -949,6 +1006,35 @@ class Search:
             bts = [[lib().fshost_search_backtrace(self.h, C.c_void_p(out[i][k:k + 1].ctypes.data)).decode() for k in range(len(out[i]))] for i in range(nq)]
             return out, bts
         return out
+
+    def exhaustive_batch(self, qAAs, q3dis, identity=None, with_backtrace=False):
+        """fshost_search_exhaustive_batch: every query against EVERY target of the database (Foldseek's --exhaustive-search 1): the score cutoff of the
+        first e-value gate per query, one database-wide forward pass with the selection on the device, the survivors through align_batch's body.
+        Returns what align_batch returns over target_id_lists = [range(n)] * nq; last_survivors holds the number of targets that reached the aligner
+        per query.  Params.maxRejected other than INT_MAX raises FsgpuError with .rc == FSGPU_E_UNSUPPORTED."""
+        nq = len(q3dis)
+        qa = [np.ascontiguousarray(x, np.uint8) for x in qAAs]
+        q3 = [np.ascontiguousarray(x, np.uint8) for x in q3dis]
+        P = C.c_void_p * max(nq, 1)
+        pa, p3, pr = P(*[x.ctypes.data for x in qa]), P(*[x.ctypes.data for x in q3]), P()
+        Ls = np.array([len(x) for x in q3], np.int32)
+        ident = None if identity is None else np.ascontiguousarray(identity, np.int64)
+        nres = np.zeros(max(nq, 1), np.int32)
+        rc = lib().fshost_search_exhaustive_batch(self.h, nq, C.cast(pa, C.c_void_p), C.cast(p3, C.c_void_p), _ptr(Ls), _ptr(ident), C.cast(pr, C.c_void_p), _ptr(nres))
+        if rc != 0:
+            e = FsgpuError(f"exhaustive_batch rc={rc}: {lib().fshost_search_error(self.h).decode()}")
+            e.rc = rc
+            raise e
+        surv = np.zeros(max(nq, 1), np.int64)
+        lib().fshost_search_exhaustive_survivors(self.h, _ptr(surv), nq)
+        self.last_survivors = surv[:nq].tolist()
+        views = [np.ctypeslib.as_array(C.cast(pr[i], C.POINTER(C.c_uint8)), shape=(int(nres[i]) * RESULT_DT.itemsize,)).view(RESULT_DT) if nres[i] else np.zeros(0, RESULT_DT)
+                 for i in range(nq)]
+        bts = None
+        if with_backtrace:
+            bts = [[lib().fshost_search_backtrace(self.h, C.c_void_p(v[k:k + 1].ctypes.data)).decode() for k in range(len(v))] for v in views]
+        out = [v.copy() for v in views]
+        return (out, bts) if with_backtrace else out
 
     def rescore_diagonal_batch(self, qAAs, q3dis, target_id_lists, diagonal_lists, identity=None):
         """fshost_search_rescore_diagonal_batch: structurerescorediagonal's per-query body for several queries in ONE library call.  target_id_lists[q] /

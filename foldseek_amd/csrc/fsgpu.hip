@@ -87,7 +87,7 @@ void fsgpu_destroy(fsgpu_ctx *ctx) {
                       &ctx->btSeq, &ctx->btTrace, &ctx->btBlocks, &ctx->btOut, &ctx->btIn, &ctx->ldIn, &ctx->ldNorm, &ctx->ldCols, &ctx->ldOut,
                       &ctx->tmIn, &ctx->tmPairs, &ctx->tmMasks, &ctx->tmOut, &ctx->tmParts,
                       &ctx->mqPssm, &ctx->mqScores, &ctx->mqQueues, &ctx->mqRec, &ctx->mqHist, &ctx->mqBaseGt, &ctx->mqBaseTie, &ctx->mqMeta,
-                      &ctx->mqOutId, &ctx->mqOutScore, &ctx->mqIdent};
+                      &ctx->mqOutId, &ctx->mqOutScore, &ctx->mqIdent, &ctx->scanCnt, &ctx->scanMeta, &ctx->scanOut};
     for (DevBuf *b : bufs) if (b->p) hipFree(b->p);
     hipFree(ctx->dMeta); hipFree(ctx->queue);
     hipHostFree(ctx->hMeta); hipHostFree(ctx->hOutId.p); hipHostFree(ctx->hOutScore.p);
@@ -95,6 +95,8 @@ void fsgpu_destroy(fsgpu_ctx *ctx) {
     hipHostFree(ctx->hS3pass.p); hipHostFree(ctx->hS3build.p); hipHostFree(ctx->hS3res.p);
     hipHostFree(ctx->hBtIn.p); hipHostFree(ctx->hBtOut.p); hipHostFree(ctx->hLdIn.p); hipHostFree(ctx->hLdOut.p);
     hipHostFree(ctx->hTmIn.p); hipHostFree(ctx->hTmOut.p);
+    hipHostFree(ctx->hScanMeta.p); hipHostFree(ctx->hScanOut.p);
+    for (int i = 0; i < 4; i++) if (ctx->scanEv[i]) (void) hipEventDestroy(ctx->scanEv[i]);
     for (int i = 0; i < 3; i++) if (ctx->tmEv[i]) (void) hipEventDestroy(ctx->tmEv[i]);
     for (int i = 0; i < 4; i++) if (ctx->tmSpEv[i]) (void) hipEventDestroy(ctx->tmSpEv[i]);
     for (int i = 0; i < 3; i++) if (ctx->ldEv[i]) (void) hipEventDestroy(ctx->ldEv[i]);
@@ -140,6 +142,7 @@ double fsgpu_last_kernel_ms(const fsgpu_ctx *ctx, int which) {
     if (ctx && (which == 14 || which == 15)) return ctx->ldMs[which - 14];
     if (ctx && (which == 16 || which == 17)) return ctx->tmMs[which - 16];
     if (ctx && which >= 18 && which <= 20) return ctx->tmSpMs[which - 18];
+    if (ctx && which >= 21 && which <= 23) return ctx->scanMs[which - 21];
     if (!ctx || which < 0 || which > 1 || !ctx->evValid[which]) return -1.0;
     if (which == 0 && ctx->mqScanMs >= 0) return ctx->mqScanMs;      // a multi-query call with row-tiled queries: all of its scans
     float ms = 0;

@@ -56,6 +56,11 @@ struct DbStore {
     struct ItemList { uint4 *items = nullptr; uint32_t n = 0; bool needsClear = false, built = false; };   // needsClear: the plan does not store every target's score byte (see gaplessItems)
     ItemList itemLists[kGaplessMaxRUntiled + 1];
     std::mutex itemMutex;
+    // fsgpu_sw_scan_c: all target ids, longest first (fs_scan_order.h), and their device copy; built on first use under itemMutex, shared by all
+    // contexts of this DB
+    std::vector<uint32_t> hScanOrder;
+    uint32_t *dScanOrder = nullptr;
+    bool scanOrderBuilt = false;
     // multi-query scans of the contexts sharing this DB run one after the other ON THE DEVICE: a context enqueues its scan
     // launches behind the event the previous batch's owner recorded after its last scan launch (fsgpu_gapless_scan_multi).
     // The mutex only orders the enqueueing (microseconds), not the execution.
@@ -63,6 +68,7 @@ struct DbStore {
     hipEvent_t lastScanDone = nullptr;     // owned by the context that recorded it (ctx->scanDoneEv)
     ~DbStore() {
         for (ItemList &l : itemLists) (void) hipFree(l.items);
+        (void) hipFree(dScanOrder);
         (void) hipFree(scan); (void) hipFree(stripeOff); (void) hipFree(stripeLen); (void) hipFree(stripeTargets);
         (void) hipFree(aln3di); (void) hipFree(alnAA); (void) hipFree(raw3di); (void) hipFree(dOffsets); (void) hipFree(dLengths);
     }
@@ -141,6 +147,13 @@ struct fsgpu_ctx {
     std::vector<uint32_t> s3ImgOff;                // per query of the call the images were built for: dword offset of its images
     uint32_t s3Plan[12] = {};                      // what the last compact call planned and ran (fsgpu_sw3_last_plan)
     PinBuf hRes0, hRes1;                           // pinned result staging
+    // fsgpu_sw_scan_c (k_sw_scan.hpp): survivors per 4096-slot chunk, [cutoffs | survivors per query | output bases], the compacted [ids | records];
+    // the staging of the last two; device ms of the last call (its SW launches, k_sw_scan_count + _offsets, k_sw_scan_emit) and its counters
+    DevBuf scanCnt, scanMeta, scanOut;
+    PinBuf hScanMeta, hScanOut;
+    hipEvent_t scanEv[4] = {nullptr, nullptr, nullptr, nullptr};
+    double scanMs[3] = {-1, -1, -1};
+    double scanStats[8] = {};
     int btWgPerCU = 0;                          // fsgpu_block_backtrace_footprint: workgroups per CU of k_block_backtrace (0: default)
     DevBuf btSeq, btTrace, btBlocks, btOut, btIn;  // fsgpu_block_backtrace (k_btrace.hpp): padded reversed prefixes, trace words, block lists, [backtraces | results], inputs
     PinBuf hBtIn, hBtOut;

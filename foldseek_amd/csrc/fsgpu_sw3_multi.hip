@@ -8,6 +8,7 @@
 #include "fsgpu_ctx.h"
 #include "k_sw3.hpp"
 #include "fsgpu_sw3.h"
+#include "fsgpu_sw3_plan.h"
 
 // ---- compact-query form of fsgpu_sw_multi_dir: k_sw3 over device-built images ---------------------------------------------------
 // A structurealign profile is matrix column + position bias (StructureSmithWaterman.cpp:1566-1640), so a query is given by its codes and
@@ -33,66 +34,38 @@ static void sw3Materialize(const int8_t *mat, const uint8_t *codes, const int8_t
 
 constexpr int kShapeHL[3] = {16, 32, 64};       // lanes per target pair of the three shapes
 
-struct Sw3Prof { std::vector<int16_t> aF, sF, aR, sR; };
+void Sw3Plan::profilesOf(int i, Sw3Prof &pr) const {
+    sw3Materialize(mat3Di, q[i].q3Di, q[i].cb3Di_fwd, q[i].L, false, pr.sF);
+    sw3Materialize(mat3Di, q[i].q3Di, q[i].cb3Di_rev, q[i].L, true, pr.sR);
+    if (hasAA) { sw3Materialize(matAA, q[i].qAA, q[i].cbAA_fwd, q[i].L, false, pr.aF); sw3Materialize(matAA, q[i].qAA, q[i].cbAA_rev, q[i].L, true, pr.aR); }
+}
 
-// One submission: the call's arguments and what the steps below (sw3*, in the order sw3MultiImpl runs them) work out about it.
-struct Sw3Plan {
-    const int8_t *mat3Di, *matAA;
-    const fsgpu_sw_cquery *q;
-    int nq, gapOpen, gapExtend, dir;                  // dir 0 / 1: one direction into out; dir 2: both directions in ONE submission (forward into out, reversed into out2)
-    const int32_t *const *sel;
-    const int32_t *nsel;
-    fsgpu_swres *out, *out2;
-    bool hasAA;
-    int slot, nDirs, dir0;                            // accounting slot of fsgpu_sw_last_passes; directions of the submission and the first of them
-    hipStream_t S;                                    // everything of the k_sw3 path: uploads, image build, launches, download
-    std::vector<size_t> base, sbase;                  // offsets into out[] (all pairs of a query) / into the pass (the selected pairs of the k_sw3 queries)
-    size_t total = 0;                                 // pairs of the pass
-    std::vector<int> cR;                              // > 0: the query runs through k_sw3
-    std::vector<int> classic;                         // the others
-    double clMs = 0, clCells = 0, clPairs = 0, clSteps = 0;          // what their sub-call ran
-    // pairs [0, nLong) of a query's sorted list (perm) run with 64 lanes, [nLong, nLong + nMid) with 32, the rest with 16
-    std::vector<uint32_t> perm;
-    std::vector<int> nLong, nMid;
-    struct Part { int q, key, R, first, n; };         // pairs [first, first + n) of query q's sorted list run with R rows per lane in launch group `key`
-    std::vector<Part> parts;
-    struct Group { int key, HL, rlo, maxR, waves, lds; size_t blk0, nblk; };
-    std::vector<Group> groups;
-    size_t nBlocks = 0, descOff = 0;                  // workgroup descriptors of the pass and their byte offset in s3pass (behind the target ids)
-
-    int nSelAll(int i) const { return sel ? (int) nsel[i] : q[i].n; }
-    int selIdx(int i, int k) const { return sel ? sel[i][k] : k; }
-    int nSel(int i) const { return cR[i] > 0 ? nSelAll(i) : 0; }
-    int nShape(int i, int shape) const { return shape == 2 ? nLong[i] : shape == 1 ? nMid[i] : nSel(i) - nLong[i] - nMid[i]; }
-    int firstOfShape(int i, int shape) const { return shape == 2 ? 0 : shape == 1 ? nLong[i] : nLong[i] + nMid[i]; }
-    void profilesOf(int i, Sw3Prof &pr) const {
-        sw3Materialize(mat3Di, q[i].q3Di, q[i].cb3Di_fwd, q[i].L, false, pr.sF);
-        sw3Materialize(mat3Di, q[i].q3Di, q[i].cb3Di_rev, q[i].L, true, pr.sR);
-        if (hasAA) { sw3Materialize(matAA, q[i].qAA, q[i].cbAA_fwd, q[i].L, false, pr.aF); sw3Materialize(matAA, q[i].qAA, q[i].cbAA_rev, q[i].L, true, pr.aR); }
-    }
-};
-
-static int sw3Validate(fsgpu_ctx *ctx, Sw3Plan &p) {
+int sw3Validate(fsgpu_ctx *ctx, Sw3Plan &p) {
     int rc;
     if ((rc = swCheckCall(ctx, p.gapOpen, p.gapExtend)) != FSGPU_OK) return rc;
-    if (p.nq > 65535) { ctx->err = "fsgpu_sw_multi_dir_c: more than 65535 queries in one call"; return FSGPU_E_ARG; }
+    const std::string who = p.who;
+    if (p.nq > 65535) { ctx->err = who + ": more than 65535 queries in one call"; return FSGPU_E_ARG; }
     if (p.hasAA && !ctx->db->hasAA) { ctx->err = "AA matrix given but the database was loaded without AA sequences"; return FSGPU_E_NODB; }
     const fsgpu_sw_cquery *q = p.q;
     p.base.assign(p.nq + 1, 0);
     for (int i = 0; i < p.nq; i++) {
-        if (!q[i].q3Di || (p.hasAA && !q[i].qAA) || q[i].L <= 0 || q[i].L > FSGPU_MAX_SEQ_LEN || q[i].n < 0 || (q[i].n > 0 && !q[i].targetIds)) { ctx->err = "fsgpu_sw_multi_dir_c: bad query"; return FSGPU_E_ARG; }
-        for (int k = 0; k < q[i].L; k++) if (q[i].q3Di[k] >= kAlphabet || (p.hasAA && q[i].qAA[k] >= kAlphabet)) { ctx->err = "fsgpu_sw_multi_dir_c: residue code out of range"; return FSGPU_E_ARG; }
+        if (!q[i].q3Di || (p.hasAA && !q[i].qAA) || q[i].L <= 0 || q[i].L > FSGPU_MAX_SEQ_LEN || q[i].n < 0 || (q[i].n > 0 && !q[i].targetIds)) { ctx->err = who + ": bad query"; return FSGPU_E_ARG; }
+        for (int k = 0; k < q[i].L; k++) if (q[i].q3Di[k] >= kAlphabet || (p.hasAA && q[i].qAA[k] >= kAlphabet)) { ctx->err = who + ": residue code out of range"; return FSGPU_E_ARG; }
         p.base[i + 1] = p.base[i] + (size_t) q[i].n;
-        if ((rc = swCheckPairs(ctx, "fsgpu_sw_multi_dir_c", q[i].targetIds, q[i].n, p.sel != nullptr, p.sel ? p.sel[i] : nullptr, p.nSelAll(i))) != FSGPU_OK) return rc;
+        if ((rc = swCheckPairs(ctx, p.who, q[i].targetIds, q[i].n, p.sel != nullptr, p.sel ? p.sel[i] : nullptr, p.nSelAll(i))) != FSGPU_OK) return rc;
     }
     return FSGPU_OK;
 }
 
 // ---- queries outside k_sw3's classes: the profile-based path, all of them in one sub-call (the same set in both directions) ----
-static int sw3Classic(fsgpu_ctx *ctx, Sw3Plan &p) {
-    const fsgpu_sw_cquery *q = p.q;
+void sw3Classify(Sw3Plan &p) {
     p.cR.assign(p.nq, 0);
-    for (int i = 0; i < p.nq; i++) { int hl; if (!sw3Class(q[i].L, p.cR[i], hl)) { p.cR[i] = 0; p.classic.push_back(i); } }
+    p.classic.clear();
+    for (int i = 0; i < p.nq; i++) { int hl; if (!sw3Class(p.q[i].L, p.cR[i], hl)) { p.cR[i] = 0; p.classic.push_back(i); } }
+}
+int sw3Classic(fsgpu_ctx *ctx, Sw3Plan &p) {
+    const fsgpu_sw_cquery *q = p.q;
+    sw3Classify(p);
     if (p.classic.empty()) return FSGPU_OK;
     const size_t nc = p.classic.size();
     std::vector<Sw3Prof> prof(nc);
@@ -146,7 +119,7 @@ static int sw3Classic(fsgpu_ctx *ctx, Sw3Plan &p) {
 // busiest (a batch of 1024 queries solo: 16 lanes 1.42 ms, 32 lanes 1.03 ms, 64 lanes 0.88 ms).  Hence the automatic rule: a call whose lists
 // hold at most 16 pairs on average runs with 64 lanes per pair throughout; the 16-lane shape is taken when the call holds at least 100 000 pairs.
 // FSGPU_SW3_MID=<columns> forces the 16-lane shape for every query (0: never), FSGPU_SW3_SHORT=<pairs> moves the short-list limit (0: off).
-static void sw3SortAndSplit(fsgpu_ctx *ctx, Sw3Plan &p) {
+void sw3SortAndSplit(fsgpu_ctx *ctx, Sw3Plan &p) {
     static const int longT = [] { const char *e = getenv("FSGPU_SW3_LONG"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 896; }();
     const int midEnv = [] { const char *e = getenv("FSGPU_SW3_MID"); return e && *e ? atoi(e) : -1; }();      // read per call: the tests switch shapes inside one process
     const int midT = midEnv >= 0 ? midEnv : 512;
@@ -154,7 +127,7 @@ static void sw3SortAndSplit(fsgpu_ctx *ctx, Sw3Plan &p) {
     static const int maxR16 = [] { const char *e = getenv("FSGPU_SW3_MAXR16"); const int v = e ? atoi(e) : 0; return v > 0 && v <= kSw3MaxR16 ? v : kSw3MaxR16; }();
     const std::vector<int32_t> &len = ctx->db->hLengths;
     const fsgpu_sw_cquery *q = p.q;
-    p.perm.resize(p.total);
+    if (!p.allOrder) p.perm.resize(p.total);
     p.nLong.assign(p.nq, 0); p.nMid.assign(p.nq, 0);
     // the short-list rule is per CALL (mean pairs per query of the call): a per-query rule left all-vs-all's batches with 64-lane groups for the short
     // lists AND 32-lane groups for the others -- 1.29 ms per batch against 0.88 ms with one shape for the whole call
@@ -162,13 +135,18 @@ static void sw3SortAndSplit(fsgpu_ctx *ctx, Sw3Plan &p) {
     for (int i = 0; i < p.nq; i++) if (p.nSel(i) > 0) nActive++;
     const bool callShort = shortList > 0 && nActive > 0 && p.total <= (size_t) shortList * nActive;
     std::vector<uint64_t> lkey;
+    // the presorted order: the targets above a threshold are a prefix of it
+    auto longerThan = [&](int t) { return (int) (std::partition_point(p.allOrder, p.allOrder + p.allN, [&](uint32_t id) { return len[id] > t; }) - p.allOrder); };
+    const int allLong = p.allOrder ? longerThan(longT) : 0, allMid = p.allOrder ? longerThan(midT) - std::min(allLong, longerThan(midT)) : 0;
     for (int i = 0; i < p.nq; i++) {
         const int ns = p.nSel(i);
         if (ns == 0) continue;
-        uint32_t *pm = p.perm.data() + p.sbase[i];
-        swSortLongestFirst(len, q[i].targetIds, p.sel ? p.sel[i] : nullptr, ns, lkey, pm);
-        int nl = 0, nm = 0;
-        for (int k = 0; k < ns; k++) { const int lt = len[q[i].targetIds[pm[k]]]; if (lt > longT) nl++; else if (lt > midT) nm++; }
+        int nl = allLong, nm = allMid;
+        if (!p.allOrder) {
+            uint32_t *pm = p.perm.data() + p.sbase[i];
+            swSortLongestFirst(len, q[i].targetIds, p.sel ? p.sel[i] : nullptr, ns, lkey, pm);
+            for (int k = 0; k < ns; k++) { const int lt = len[q[i].targetIds[pm[k]]]; if (lt > longT) nl++; else if (lt > midT) nm++; }
+        }
         p.nLong[i] = (q[i].L > 32 * kSw3MaxR || callShort) ? ns : nl;
         const bool shape16 = q[i].L <= 16 * maxR16 && midT > 0 && (midEnv >= 0 || p.total >= 100000);
         p.nMid[i] = p.nLong[i] == ns ? 0 : shape16 ? nm : ns - p.nLong[i];
@@ -176,7 +154,7 @@ static void sw3SortAndSplit(fsgpu_ctx *ctx, Sw3Plan &p) {
 }
 
 // images: built once per set of queries (the reversed call of a forward call finds them in place)
-static int sw3Images(fsgpu_ctx *ctx, const Sw3Plan &p) {
+int sw3Images(fsgpu_ctx *ctx, const Sw3Plan &p) {
     const fsgpu_sw_cquery *q = p.q;
     const int nq = p.nq;
     const bool hasAA = p.hasAA;
@@ -246,11 +224,11 @@ static int sw3Images(fsgpu_ctx *ctx, const Sw3Plan &p) {
                              (uint32_t *) ctx->s3img.p, hasAA, p.S);
     if (rc != FSGPU_OK) return rc;
     ctx->s3Sig = sig;
-    ctx->s3Plan[8] = (uint32_t) nImg;
+    ctx->s3Plan[8] += (uint32_t) nImg;
     return FSGPU_OK;
 }
 
-static void sw3Groups(Sw3Plan &p) {
+void sw3Groups(Sw3Plan &p) {
     const bool hasAA = p.hasAA;
     // launch groups: lanes per target pair x kernel (R = 1..8 / 9..16 / 17..24) x LDS occupancy class of the R range of four (the dynamic LDS of a
     // launch is that of its largest R: a query of 9 rows per lane must not take the 106 KB of one with 16 and lose its second workgroup per CU)
@@ -282,33 +260,37 @@ static void sw3Groups(Sw3Plan &p) {
 }
 
 // the view of the plan that fsgpu_sw3_last_plan hands out: counters only, nothing here feeds a launch
-static void sw3RecordPlan(fsgpu_ctx *ctx, const Sw3Plan &p) {
+void sw3RecordPlan(fsgpu_ctx *ctx, const Sw3Plan &p) {
     uint32_t *o = ctx->s3Plan;
     for (const Sw3Plan::Part &pt : p.parts) {
         const int shape = pt.key / 12;
         o[shape] += (uint32_t) pt.n;
         o[3 + shape] |= 1u << pt.R;
     }
-    o[9] = (uint32_t) p.groups.size();
-    o[10] = (uint32_t) p.nBlocks;
+    o[9] += (uint32_t) p.groups.size();           // (+=: the sub-batches of a scan add up; every other call starts from zeroed counters)
+    o[10] += (uint32_t) p.nBlocks;
 }
 
 // target ids and workgroup descriptors of the pass, with the accounting for fsgpu_sw_last_passes; uploads both
-static int sw3Descriptors(fsgpu_ctx *ctx, Sw3Plan &p) {
+int sw3Descriptors(fsgpu_ctx *ctx, Sw3Plan &p) {
     const fsgpu_sw_cquery *q = p.q;
     const std::vector<int32_t> &len = ctx->db->hLengths;
     const size_t total = p.total;
     int rc;
     p.descOff = (total * 4 + 15) / 16 * 16;
     const size_t passBytes = p.descOff + p.nBlocks * sizeof(SwBlockDesc);
-    if ((rc = ensurePinnedAll(ctx, {{ctx->hS3pass, passBytes}, {ctx->hS3res, total * 16 * p.nDirs}})) != FSGPU_OK) return rc;
+    // presorted: neither the ids nor the records pass through the host, the staging holds the descriptors alone
+    const size_t hostOff = p.allOrder ? 0 : p.descOff;
+    if ((rc = ensurePinnedAll(ctx, {{ctx->hS3pass, passBytes - p.descOff + hostOff}, {ctx->hS3res, p.allOrder ? 0 : total * 16 * p.nDirs}})) != FSGPU_OK) return rc;
     if ((rc = ensureAll(ctx, {{ctx->s3pass, passBytes}, {ctx->s3res, total * 16 * p.nDirs}})) != FSGPU_OK) return rc;
     uint32_t *hTids = (uint32_t *) ctx->hS3pass.p;
-    SwBlockDesc *hBlk = (SwBlockDesc *) ((unsigned char *) ctx->hS3pass.p + p.descOff);
-    for (int i = 0; i < p.nq; i++) {
+    SwBlockDesc *hBlk = (SwBlockDesc *) ((unsigned char *) ctx->hS3pass.p + hostOff);
+    for (int i = 0; i < p.nq && !p.allOrder; i++) {
         const uint32_t *pm = p.perm.data() + p.sbase[i];
         for (int k = 0; k < p.nSel(i); k++) hTids[p.sbase[i] + k] = q[i].targetIds[pm[k]];
     }
+    // target id of a pair of the pass (presorted: every query's pairs are the whole order, sbase is a multiple of allN)
+    auto tidOfPair = [&](size_t pair) { return p.allOrder ? p.allOrder[pair % (size_t) p.allN] : hTids[pair]; };
     double cells = 0, pairs = 0, winsts = 0;
     for (const Sw3Plan::Group &g : p.groups) {
         const int ppb = g.waves * 2 * (64 / g.HL), ppw = 2 * (64 / g.HL);
@@ -323,7 +305,7 @@ static int sw3Descriptors(fsgpu_ctx *ctx, Sw3Plan &p) {
             }
             // accounting in the units of the kernel's roofline: DP cells and the VALU wave-instructions its waves issue (a wave runs
             // (longest of its targets) + lanes - 1 steps of 14 packed instructions per register row + 16 around them [+ the AA adds])
-            const uint32_t *tp = hTids + p.sbase[i] + pt.first;
+            const uint32_t *tp = p.allOrder ? p.allOrder + pt.first : hTids + p.sbase[i] + pt.first;
             const double perStep = 14.0 * pt.R + 16.0 + (p.hasAA ? 2.0 * sw3Dw(pt.R) + 4.0 : 0.0);
             for (int k = 0; k < pt.n; k++) {
                 const int lt = len[tp[k]];
@@ -336,21 +318,21 @@ static int sw3Descriptors(fsgpu_ctx *ctx, Sw3Plan &p) {
         // rows per lane runs twice the instructions per column of one with 7)
         const int hl = g.HL;
         auto work = [&](const SwBlockDesc &x) {
-            const long lt = len[hTids[x.firstPair]];
+            const long lt = len[tidOfPair(x.firstPair)];
             const long R = ((long) x.rowsInTile + hl - 1) / hl;
             return (lt + hl) * (15 * R + 18);
         };
         std::stable_sort(hBlk + g.blk0, hBlk + g.blk0 + g.nblk, [&](const SwBlockDesc &x, const SwBlockDesc &y) { return work(x) > work(y); });
     }
     ctx->swDirCells[p.slot] = p.clCells + cells * p.nDirs; ctx->swDirPairs[p.slot] = p.clPairs + pairs * p.nDirs; ctx->swDirWaveSteps[p.slot] = p.clSteps + winsts * p.nDirs;
-    HIPCHK(hipMemcpyAsync(ctx->s3pass.p, ctx->hS3pass.p, passBytes, hipMemcpyHostToDevice, p.S));
+    HIPCHK(hipMemcpyAsync((unsigned char *) ctx->s3pass.p + p.descOff - hostOff, ctx->hS3pass.p, passBytes - p.descOff + hostOff, hipMemcpyHostToDevice, p.S));
     return FSGPU_OK;
 }
 
 // Every launch group gets a stream: their long-target tails overlap instead of queueing up
 // ... and, in the one-submission form, the two directions of a group: the forward and the reversed-query launch of all-vs-all's batches are one round of
 // waves each (0.69 ms apiece for 1024 queries x 8 pairs, the wavefront of the longest target) and ran one behind the other on the group's stream
-static int sw3Launch(fsgpu_ctx *ctx, const Sw3Plan &p) {
+int sw3Launch(fsgpu_ctx *ctx, const Sw3Plan &p) {
     hipStream_t S = p.S;
     int rc;
     if (p.slot == 0 || !ctx->evValid[1]) HIPCHK(hipEventRecord(ctx->ev[2], S));
@@ -380,6 +362,18 @@ static int sw3Launch(fsgpu_ctx *ctx, const Sw3Plan &p) {
     HIPCHK(hipEventRecord(ctx->swDirEv[2 * p.slot + 1], S));
     ctx->swDirValid[p.slot] = true;
     ctx->evValid[1] = true;
+    return FSGPU_OK;
+}
+
+int sw3BeginPass(fsgpu_ctx *ctx, Sw3Plan &p) {
+    p.sbase.assign(p.nq + 1, 0);
+    for (int i = 0; i < p.nq; i++) p.sbase[i + 1] = p.sbase[i] + (size_t) p.nSel(i);
+    p.total = p.sbase[p.nq];
+    if (!ctx->swDirEv[3]) for (int i = 0; i < 4; i++) HIPCHK(hipEventCreate(&ctx->swDirEv[i]));
+    ctx->swDirValid[p.slot] = false;
+    if (p.slot == 0) ctx->swDirValid[1] = false;
+    ctx->swDirCells[p.slot] = p.clCells; ctx->swDirPairs[p.slot] = p.clPairs; ctx->swDirWaveSteps[p.slot] = p.clSteps;
+    ctx->swDirExtraMs[p.slot] = p.clMs;
     return FSGPU_OK;
 }
 
@@ -440,23 +434,11 @@ static int sw3MultiImpl(fsgpu_ctx *ctx, const int8_t *mat3Di, const int8_t *matA
     int rc;
     if ((rc = sw3Validate(ctx, p)) != FSGPU_OK) return rc;
     HIPCHK(hipSetDevice(ctx->device));
-    // an error return after work was enqueued must not leave copies out of the pinned staging buffers or kernels in flight: the next call (or
-    // fsgpu_destroy) would refill / free memory that is still being read
-    struct Drain {
-        fsgpu_ctx *c; hipStream_t s; bool ok = false;
-        ~Drain() { if (ok) return; (void) hipStreamSynchronize(s); for (int i = 0; i < fsgpu_ctx::kSwAux; i++) if (c->swAux[i]) (void) hipStreamSynchronize(c->swAux[i]); (void) hipGetLastError(); }
-    } drain{ctx, p.S};
+    Sw3Drain drain{ctx, p.S};
     memset(ctx->s3Plan, 0, sizeof(ctx->s3Plan));
     if ((rc = sw3Classic(ctx, p)) != FSGPU_OK) return rc;
     for (int i : p.classic) ctx->s3Plan[6] += (uint32_t) p.nSelAll(i);
-    p.sbase.assign(nq + 1, 0);
-    for (int i = 0; i < nq; i++) p.sbase[i + 1] = p.sbase[i] + (size_t) p.nSel(i);
-    p.total = p.sbase[nq];
-    if (!ctx->swDirEv[3]) for (int i = 0; i < 4; i++) HIPCHK(hipEventCreate(&ctx->swDirEv[i]));
-    ctx->swDirValid[p.slot] = false;
-    if (p.slot == 0) ctx->swDirValid[1] = false;
-    ctx->swDirCells[p.slot] = p.clCells; ctx->swDirPairs[p.slot] = p.clPairs; ctx->swDirWaveSteps[p.slot] = p.clSteps;
-    ctx->swDirExtraMs[p.slot] = p.clMs;
+    if ((rc = sw3BeginPass(ctx, p)) != FSGPU_OK) return rc;
     if (p.total == 0) {
         if (!p.classic.empty()) {          // every query of the call was row-tiled: an empty k_sw3 interval carries the sub-call's figures
             HIPCHK(hipEventRecord(ctx->swDirEv[2 * p.slot], p.S)); HIPCHK(hipEventRecord(ctx->swDirEv[2 * p.slot + 1], p.S));

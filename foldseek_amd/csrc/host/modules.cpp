@@ -4,7 +4,7 @@
 //   structurealign    <queryDB> <targetDB[_pad]> <prefDB> <outAlnDB>         F/src/strucclustutils/structurealign.cpp:141-481
 //   prefilter         <queryDB_ss> <targetDB_ss[_pad]> <outPrefDB>          M/src/prefiltering/Main.cpp -> Prefiltering.cpp:22-245,755-982
 //   makepaddedseqdb   <seqDB> <outPaddedDB>                                  M/src/util/makepaddedseqdb.cpp:14-154
-//   search            <queryDB> <targetDB[_pad]> <outAlnDB> [<outPrefDB>]   prefilter + structurealign of
+//   search            <queryDB> <targetDB[_pad]> <outAlnDB> [<outPrefDB>]   prefilter (or none: --exhaustive-search 1) + structurealign of
 //                     F/data/structuresearch.sh:41-53,116-143 in ONE process: the target DB and (for the k-mer mode) its
 //                     index stay resident, no prefilter DB round trip; same result DBs
 //   gpuserver         <targetDB_ss[_pad]>                                    M/src/util/gpuserver.cpp:24-101 (resident DB, shm protocol);
@@ -126,8 +126,9 @@ const FlagSpec kStructAlignOnlyFlags[] = {     // structurealign, not structurer
 const FlagSpec kRescoreOnlyFlags[] = {         // ours: what to do with pairs whose reference result is undefined (see fsgpu.h)
     {"--undefined-diagonals", false, ONLY, "fail|skip"}, {nullptr, false, USE, nullptr}};
 
-const FlagSpec kSearchFlags[] = {              // the fused module: prefilter / ungappedprefilter + structurealign
-    {"--prefilter-mode", false, ONLY, "0|1"}, {nullptr, false, USE, nullptr}};
+const FlagSpec kSearchFlags[] = {              // the fused module: prefilter / ungappedprefilter / no prefilter at all + structurealign
+    // 2 = exhaustive: every target goes to the aligner (StructureSearch.cpp:114-127); --exhaustive-search is a bool of the reference (Parameters.cpp:187)
+    {"--prefilter-mode", false, ONLY, "0|1|2"}, {"--exhaustive-search", true, USE, "0"}, {nullptr, false, USE, nullptr}};
 
 const FlagSpec kPaddedFlags[] = {              // Parameters::makepaddedseqdb (Parameters.cpp:913-921)
     {"--score-bias", false, IGNORE, nullptr}, {"--mask", false, ONLY, "0"}, {"--mask-prob", false, IGNORE, nullptr},
@@ -1006,7 +1007,7 @@ int fsmod_prefilter(int argc, const char **argv) {
     return EXIT_SUCCESS;
 }
 
-// prefilter (k-mer: --prefilter-mode 0, gapless: --prefilter-mode 1) + structurealign fused in one process
+// prefilter (k-mer: --prefilter-mode 0, gapless: --prefilter-mode 1, none: --prefilter-mode 2 / --exhaustive-search 1) + structurealign fused in one process
 int fsmod_search(int argc, const char **argv) {
     Options o;
     {
@@ -1014,7 +1015,7 @@ int fsmod_search(int argc, const char **argv) {
         if (!parseArgs(argc, argv, "search", {kSearchFlags, kPrefilterFlags, kAlignFlags, kStructAlignOnlyFlags, kCommonFlags}, o, perr)) return fail(perr);
     }
     if (o.pos.size() != 3 && o.pos.size() != 4)
-        return fail("usage: search <queryDB> <targetDB> <outAlnDB> [<outPrefDB>] [--prefilter-mode 0|1] [-s S] [--max-seqs N] [-e E] [--alignment-type 0|2] [-a] [--threads T] ...");
+        return fail("usage: search <queryDB> <targetDB> <outAlnDB> [<outPrefDB>] [--prefilter-mode 0|1|2] [--exhaustive-search 0|1] [-s S] [--max-seqs N] [-e E] [--alignment-type 0|2] [-a] [--threads T] ...");
     std::string err;
     const double tStart = nowSec();
     std::atomic<int64_t> usPrep(0), usPref(0), usAlign(0), usFormat(0), usAlnPrep(0), usAlnDev(0), usAlnGate(0), usAlnBack(0), nRev(0), nPairs(0), nBtDev(0), nBtAll(0);
@@ -1023,8 +1024,15 @@ int fsmod_search(int argc, const char **argv) {
     if (qA.size() != q3.size()) return fail("query AA and 3Di databases differ in size");
     const bool sameDB = o.pos[0] == o.pos[1];
     const bool includeIdentical = o.geti("--add-self-matches", 0) != 0;
-    const int prefMode = o.geti("--prefilter-mode", 0);
-    if (prefMode != 0 && prefMode != 1) return fail("search: --prefilter-mode 0 (k-mer) or 1 (ungapped)");
+    // the flag wins over the mode (StructureSearch.cpp:125)
+    const int prefMode = o.geti("--exhaustive-search", 0) != 0 ? 2 : o.geti("--prefilter-mode", 0);
+    if (prefMode < 0 || prefMode > 2) return fail("search: --prefilter-mode 0 (k-mer), 1 (ungapped) or 2 (exhaustive)");
+    if (prefMode == 2) {
+        // no prefilter runs: there is no prefilter result to write, and the device drops the targets the first e-value gate rejects before the accept
+        // loop could count them as rejected
+        if (o.pos.size() == 4) return fail("search: <outPrefDB> is not written in the exhaustive mode (--prefilter-mode 2 / --exhaustive-search 1): no prefilter runs");
+        if (o.kv.count("--max-rejected")) return fail("search: --max-rejected is not supported in the exhaustive mode (--prefilter-mode 2 / --exhaustive-search 1)");
+    }
     fshost_params par;
     fillParams(o, par);
     par.prefCompBiasScale = (float) o.getd("--comp-bias-corr-scale", 0.15);    // StructureSearch.cpp:101
@@ -1170,6 +1178,44 @@ int fsmod_search(int argc, const char **argv) {
                     }
                 }
                 if (bad) break;
+                usFormat += (int64_t) ((nowSec() - t0) * 1e6);
+                continue;
+            } else if (prefMode == 2) {
+                // ---- exhaustive: the batch in one library call (fshost_search_exhaustive_batch: cutoffs, database-wide forward pass, alignment of the survivors) ----
+                std::vector<size_t> live;
+                for (size_t k = 0; k < nb; k++) if (Ls[k] > 0) live.push_back(k);
+                if (live.empty()) continue;
+                std::vector<const uint8_t *> lA, l3; std::vector<int> lL, lres(live.size()); std::vector<int64_t> lI;
+                std::vector<const fshost_result *> lR(live.size());
+                for (size_t k : live) {
+                    lA.push_back(pA[k]); l3.push_back(p3[k]); lL.push_back(Ls[k]);
+                    lI.push_back((sameDB || includeIdentical) ? (int64_t) qid[k] : -1);        // structurealign compares reader INDICES (structurealign.cpp:359)
+                }
+                if (ca.on) {
+                    std::vector<const char *> e; std::vector<uint32_t> l;
+                    for (size_t k : live) { e.push_back(caE[k]); l.push_back(caL[k]); }
+                    fshost_search_set_query_ca(s, (int) live.size(), e.data(), l.data());
+                }
+                if (fshost_search_exhaustive_batch(s, (int) live.size(), lA.data(), l3.data(), lL.data(), lI.data(), lR.data(), lres.data()) != FSGPU_OK) {
+                    if (!bad++) firstErr = fshost_search_error(s);
+                    break;
+                }
+                { const double t1 = nowSec(); usAlign += (int64_t) ((t1 - t0) * 1e6); t0 = t1; }
+                {
+                    double st[8];
+                    fshost_search_stats(s, st);
+                    usAlnPrep += (int64_t) (st[2] * 1e6); usAlnDev += (int64_t) (st[3] * 1e6); usAlnGate += (int64_t) (st[4] * 1e6); usAlnBack += (int64_t) (st[5] * 1e6);
+                    nRev += (int64_t) st[7];
+                    { int64_t bd = 0, ba = 0; fshost_search_backtrace_counts(s, &bd, &ba); nBtDev += bd; nBtAll += ba; }
+                    std::vector<int64_t> surv(live.size());
+                    fshost_search_exhaustive_survivors(s, surv.data(), (int) surv.size());
+                    for (int64_t x : surv) nPairs += x;
+                }
+                for (size_t j = 0; j < live.size(); j++) {
+                    std::string &out = results[qid[live[j]]];
+                    for (int r = 0; r < lres[j]; r++)
+                        out.append(line.data(), fshost_format_result(line.data(), &lR[j][r], fshost_search_backtrace(s, &lR[j][r]), par.addBacktrace));
+                }
                 usFormat += (int64_t) ((nowSec() - t0) * 1e6);
                 continue;
             } else {

@@ -52,6 +52,11 @@ struct fshost_search {
     std::vector<std::vector<int16_t>> kThr;     // fshost_search_kmer_batch: per-query k-mer thresholds / ungapped profiles of the last batch
     std::vector<std::vector<int8_t>> kProf;
     std::vector<fsgpu_kmer_query> kq;
+    // fshost_search_exhaustive_batch: the scan's survivors (ids, forward records, offsets per query) and the results of the last call
+    std::vector<uint32_t> exhIds;
+    std::vector<fsgpu_swres> exhFwd;
+    std::vector<uint64_t> exhBase;
+    std::vector<std::vector<fshost_result>> exhRes;
     // LDDT filter (fshost_search_bind_ca / fshost_search_set_query_ca): threshold, the target C-alpha entries by target index (borrowed), the query
     // entries of the next align call, the decoded query coordinates of the running one, staging of a fsgpu_lddt_batch call
     float lddtThr = 0.0f;
@@ -1052,6 +1057,66 @@ int fshost_search_align_batch(fshost_search *s, int nq, const uint8_t *const *qA
     s->stats[2] = t1 - t0; s->stats[3] = t2 - t1; s->stats[5] = tBack; s->stats[4] = nowSec() - t2 - tBack;
     s->lastDeviceBt = (int64_t) pb.onDevice; s->lastBtTasks = (int64_t) pb.outs.size();
     return FSGPU_OK;
+}
+
+// The exhaustive search (StructureSearch.cpp:114-127: no prefilter, `fake_pref` hands every target to structurealign) for nq queries: alignStructure's first
+// e-value gate as a score cutoff per query, ONE database-wide forward pass that selects against it on the device (fsgpu_sw_scan_c), and the
+// survivors -- in ascending target index, the order of fake_pref's lines -- through fshost_search_align_batch unchanged.  That body computes the forward
+// pass of the survivors again, on purpose: they are few, and the accept loop stays the one code path that the coverage gate, the reversed pass, the
+// backtraces, the LDDT / TM drops, structure bits, --alt-ali and --max-accept go through.  A dropped target is one the first e-value gate rejects, which
+// shows only in the count --max-rejected compares with: that parameter is refused here.
+int fshost_search_exhaustive_batch(fshost_search *s, int nq, const uint8_t *const *qAA, const uint8_t *const *q3di, const int *L,
+                                   const int64_t *identityId, const fshost_result **results, int *nres) {
+    if (!s || !s->ctx || nq < 0 || (nq > 0 && (!qAA || !q3di || !L || !results || !nres))) return FSGPU_E_ARG;
+    const fshost_params &par = s->par;
+    if (par.maxRejected != INT_MAX) { s->err = "exhaustive search: --max-rejected is not supported (the targets the device drops would have to be counted)"; return FSGPU_E_UNSUPPORTED; }
+    const bool useAA = par.alignmentType == 2;
+    for (int i = 0; i < nq; i++) if (!qAA[i] || !q3di[i] || L[i] <= 0) return FSGPU_E_ARG;
+    std::vector<AlignQuery> aq(nq);
+    std::vector<fsgpu_sw_cquery> dq(nq);
+    std::vector<int32_t> cutoff(nq);
+    std::vector<uint8_t> rAA, r3Di;
+    for (int i = 0; i < nq; i++) {
+        aq[i].qAA = qAA[i]; aq[i].q3di = q3di[i]; aq[i].L = L[i];
+        const int rc = prepareAlign(s, aq[i], rAA, r3Di, false);
+        if (rc != FSGPU_OK) return rc;
+        cutoff[i] = s->evaluer.scoreCutoff(aq[i].lambda, aq[i].mu, par.evalThr);
+        dq[i].qAA = qAA[i]; dq[i].q3Di = q3di[i];
+        dq[i].cbAA_fwd = aq[i].cbAA.data(); dq[i].cb3Di_fwd = aq[i].cbSS.data(); dq[i].cbAA_rev = aq[i].cbAAr.data(); dq[i].cb3Di_rev = aq[i].cbSSr.data();
+        dq[i].L = L[i]; dq[i].n = 0; dq[i].targetIds = nullptr;
+    }
+    const int8_t *m3 = s->mat3Di.tiny.data(), *mA = useAA ? s->matAA.tiny.data() : nullptr;
+    s->exhBase.assign((size_t) nq + 1, 0);
+    if (s->exhIds.size() < 4096) { s->exhIds.resize(4096); s->exhFwd.resize(4096); }
+    int rc = fsgpu_sw_scan_c(s->ctx, m3, mA, dq.data(), nq, par.gapOpen, par.gapExtend, cutoff.data(), s->exhIds.data(), s->exhFwd.data(), s->exhIds.size(), s->exhBase.data());
+    if (rc == FSGPU_E_OUTPUT) {          // the needed size was reported: grow and repeat, once
+        s->exhIds.resize(s->exhBase[nq]); s->exhFwd.resize(s->exhBase[nq]);
+        rc = fsgpu_sw_scan_c(s->ctx, m3, mA, dq.data(), nq, par.gapOpen, par.gapExtend, cutoff.data(), s->exhIds.data(), s->exhFwd.data(), s->exhIds.size(), s->exhBase.data());
+    }
+    if (rc != FSGPU_OK) { s->err = fsgpu_last_error(s->ctx); return rc; }
+    std::vector<const uint32_t *> tids(nq);
+    std::vector<int> n(nq);
+    std::vector<fshost_result *> res(nq);
+    s->exhRes.resize(nq);
+    for (int i = 0; i < nq; i++) {
+        const uint64_t cnt = s->exhBase[i + 1] - s->exhBase[i];
+        if (cnt > (uint64_t) INT_MAX / (1 + (uint64_t) std::max(0, par.altAlignment))) { s->err = "exhaustive search: too many survivors for one query"; return FSGPU_E_NOMEM; }
+        tids[i] = s->exhIds.data() + s->exhBase[i]; n[i] = (int) cnt;
+        s->exhRes[i].resize(std::max<size_t>(1, (size_t) cnt * (1 + std::max(0, par.altAlignment))));
+        res[i] = s->exhRes[i].data();
+    }
+    rc = fshost_search_align_batch(s, nq, qAA, q3di, L, identityId, tids.data(), n.data(), res.data(), nres);
+    if (rc != FSGPU_OK) return rc;
+    for (int i = 0; i < nq; i++) results[i] = s->exhRes[i].data();
+    return FSGPU_OK;
+}
+
+// survivors per query of the last fshost_search_exhaustive_batch (the targets that reached the aligner); returns the number of queries of that call
+int fshost_search_exhaustive_survivors(const fshost_search *s, int64_t *out, int cap) {
+    if (!s) return 0;
+    const int nq = s->exhBase.empty() ? 0 : (int) s->exhBase.size() - 1;
+    for (int i = 0; i < nq && i < cap && out; i++) out[i] = (int64_t) (s->exhBase[i + 1] - s->exhBase[i]);
+    return nq;
 }
 
 // structurerescorediagonal's per-query body (F/src/strucclustutils/structurerescorediagonal.cpp:50-156, 300-370) for nq queries:

@@ -53,7 +53,8 @@ enum {
     FSGPU_E_HIP = -2,        /* a HIP runtime call failed (text in fsgpu_last_error) */
     FSGPU_E_NODB = -3,       /* no database loaded / AA part missing */
     FSGPU_E_UNSUPPORTED = -4,/* parameter combination not implemented on the device path */
-    FSGPU_E_NOMEM = -5
+    FSGPU_E_NOMEM = -5,
+    FSGPU_E_OUTPUT = -6      /* the caller's output buffer is too small; the needed sizes were reported, call again */
 };
 
 typedef struct fsgpu_ctx fsgpu_ctx;
@@ -249,6 +250,23 @@ int fsgpu_sw_multi_dir_c(fsgpu_ctx *ctx, const int8_t *mat3Di, const int8_t *mat
  * host between two passes.  fwd / rev as in fsgpu_sw_multi. */
 int fsgpu_sw_multi_c(fsgpu_ctx *ctx, const int8_t *mat3Di, const int8_t *matAA, const fsgpu_sw_cquery *q, int nq, int gapOpen, int gapExtend,
                      fsgpu_swres *fwd, fsgpu_swres *rev);
+/* Exhaustive search (Foldseek's --exhaustive-search 1 / search --prefilter-mode 2: no prefilter, every target goes to structurealign,
+ * F/src/workflow/StructureSearch.cpp:114-127): the forward pass of every query against EVERY target of the database, selected on the device against
+ * a score cutoff per query (fshost_evalue_score_cutoff: alignStructure's first e-value gate, structurealign.cpp:55-59).
+ * q[] as for fsgpu_sw_multi_dir_c with n = 0 and targetIds = NULL.  For every query i the answer is outIds[outBase[i] .. outBase[i + 1]) in ascending
+ * target id with the forward records in outFwd at the same places: exactly what fsgpu_sw_multi_dir_c(dir 0) returns for targetIds = 0 .. N-1,
+ * restricted to the pairs with score >= cutoff[i] (the int32 re-run included: its score decides).  An empty target scores 0.
+ * cap: room in outIds / outFwd, in records.  When the survivors of the call exceed it the call returns FSGPU_E_OUTPUT: outBase[0 .. nq] holds the
+ * offsets that were needed (outBase[nq] = the total), nothing is written at or beyond cap, and the caller may call again with larger buffers.
+ * A cutoff outside 0..32767 is FSGPU_E_ARG.  Queries are run in sub-batches of 20 bytes x N per query under a budget of 1 GiB
+ * (FSGPU_SCAN_BYTES=<bytes>, read per call); the order of the targets is sorted once per database.  Queries of more than 1024 residues take the
+ * profile path in chunks of targets and are filtered on the host: correct, not fast.  fsgpu_sw3_last_plan and fsgpu_sw_last_passes (forward slot)
+ * report the whole call. */
+int fsgpu_sw_scan_c(fsgpu_ctx *ctx, const int8_t *mat3Di, const int8_t *matAA, const fsgpu_sw_cquery *q, int nq, int gapOpen, int gapExtend,
+                    const int32_t *cutoff, uint32_t *outIds, fsgpu_swres *outFwd, uint64_t cap, uint64_t *outBase);
+/* out[8] of the last fsgpu_sw_scan_c: [0] sub-batches, [1] records the device selection handed to the host (survivors and int16-saturated pairs),
+ * [2] host ms spent planning the sub-batches, [3] survivors, [4] host ms of the whole call, [5..7] 0. */
+void fsgpu_sw_scan_last(const fsgpu_ctx *ctx, double *out8);
 /* Asynchronous halves of fsgpu_sw_batch.  The four profile arrays and targetIds are BORROWED until fsgpu_sw_finish returns
  * (the int32 re-run of saturated pairs reads the profiles again); after a failed _launch nothing is pending. */
 int fsgpu_sw_launch(fsgpu_ctx *ctx, const int16_t *pAA_fwd, const int16_t *p3Di_fwd,
@@ -501,7 +519,8 @@ int fsgpu_kmer_plan_coarse(const int32_t *lengths, uint64_t n, uint32_t blocksPe
  * detection per segment, scoring, replay, selection), 11 host tail, 12 the index-probe kernel (k_kmer_lists) alone,
  * 14 / 15 the two kernels of the last fsgpu_lddt_batch (k_lddt_norm, k_lddt_pairs),
  * 16 / 17 the two kernels of the last fsgpu_tm_batch (k_tm_pairs, k_tm_search),
- * 18 / 19 / 20 the three kernels of the last fsgpu_tm_superpose_batch (k_tm_pairs, k_tm_sp_search, k_tm_sp_finish).
+ * 18 / 19 / 20 the three kernels of the last fsgpu_tm_superpose_batch (k_tm_pairs, k_tm_sp_search, k_tm_sp_finish),
+ * 21 / 22 / 23 of the last fsgpu_sw_scan_c, summed over its sub-batches: the Smith-Waterman launches, k_sw_scan_count + k_sw_scan_offsets, k_sw_scan_emit.
  * Returns < 0 if nothing was recorded. */
 double fsgpu_last_kernel_ms(const fsgpu_ctx *ctx, int which);
 /* Read-only record of the choices a context makes from what it ran before (for tests; nothing reads it back): out8[0] / [1] the form the count pass

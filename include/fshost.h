@@ -85,7 +85,7 @@ double fshost_evalue_corr(const fshost_evaluer *e, double score, double lambda, 
  * fshost_evalue_corr(e, s, lambda, mu) <= evalThr (a NaN e-value counts as passing, as it does at the gate), 32767 when there is none.  Found
  * by evaluating the function at every s from 0 upwards, not by inverting it: every score below the cutoff is one the gate rejects, whatever
  * branch of computePvalue it falls in.  What a database-wide forward pass needs to drop targets on the device before the aligner sees them
- * (the exhaustive search, StructureSearch.cpp:114-127; not built yet). */
+ * (the exhaustive search, StructureSearch.cpp:114-127: fshost_search_exhaustive_batch hands it to fsgpu_sw_scan_c). */
 int fshost_evalue_score_cutoff(const fshost_evaluer *e, double lambda, double mu, double evalThr);
 
 /* ---- one query through prefilter + structurealign (what bench.py times and the module executables call) ---- */
@@ -155,6 +155,16 @@ int fshost_search_align(fshost_search *s, const uint8_t *qAA, const uint8_t *q3d
 int fshost_search_align_batch(fshost_search *s, int nq, const uint8_t *const *qAA, const uint8_t *const *q3di, const int *L,
                               const int64_t *identityId, const uint32_t *const *targetIds, const int *n,
                               fshost_result *const *results, int *nres);
+/* Exhaustive search (--exhaustive-search 1 / search --prefilter-mode 2, F/src/workflow/StructureSearch.cpp:114-127: no prefilter, every target goes to
+ * structurealign): per query mu / lambda and the score cutoff of alignStructure's first e-value gate (fshost_evalue_score_cutoff at the handle's evalThr),
+ * one database-wide forward pass with the selection on the device (fsgpu_sw_scan_c), and the survivors, in ascending target index, through the body of
+ * fshost_search_align_batch.  Arguments as there without the target lists; results[q] receives a pointer to nres[q] records owned by the handle (they and
+ * their backtraces stay valid until the next align call).  The answer is that of fshost_search_align_batch over targetIds = 0 .. N-1.  A handle whose
+ * maxRejected is not INT_MAX is refused (FSGPU_E_UNSUPPORTED): the rejected count would need the dropped targets.  Returns 0 or < 0. */
+int fshost_search_exhaustive_batch(fshost_search *s, int nq, const uint8_t *const *qAA, const uint8_t *const *q3di, const int *L,
+                                   const int64_t *identityId, const fshost_result **results, int *nres);
+/* survivors per query of the last fshost_search_exhaustive_batch (targets handed to the aligner), out[0 .. min(cap, queries)); returns the queries of that call */
+int fshost_search_exhaustive_survivors(const fshost_search *s, int64_t *out, int cap);
 /* The per-batch body of the fused `search` module with the k-mer prefilter, in ONE call: query profiles and k-mer thresholds
  * (fshost_kmer_query_prepare), the device prefilter (fsgpu_kmer_search: QueryMatcher::matchQuery, M/src/prefiltering/QueryMatcher.cpp:103-240),
  * runSplit's coverage pre-filter of its hits (Util::canBeCovered for --cov-mode 0 / 2 / 5, M/src/prefiltering/Prefiltering.cpp:880-887) and the
