@@ -24,7 +24,10 @@ constexpr int kGaplessMaxRUntiled = 56;
 #define FSGPU_GAPLESS_BIGBLOCK (2 * FSGPU_GAPLESS_BLOCK)
 #endif
 __host__ __device__ constexpr int gaplessBlockThreads(int R) { return R <= 36 ? kGaplessBlock : FSGPU_GAPLESS_BIGBLOCK; }
-constexpr int kSwMaxR = 8;             // register rows per lane in the SW wavefront -> 64*R <= 512 rows per tile
+// Two queries per register (k_gapless HALVES): the classes of the 4-wave workgroups beyond the paired short ones
+constexpr int kGaplessHalvesMinR = kGaplessMaxR / 2 + 1, kGaplessHalvesMaxR = 36;
+constexpr int kGaplessHalvesPromote = 2;   // an odd member out may ride as query B of a class at most this many registers up (fsgpu_gapless_pair_halves)
+constexpr int kSwMaxR = 8;            // register rows per lane in the SW wavefront -> 64*R <= 512 rows per tile
 constexpr uint32_t kFloor2 = 0x80008000u; // packed (INT16_MIN, INT16_MIN): the gapless recurrence's "zero"
 
 // ------------------------------------------------------------------------------------------------------------
@@ -35,6 +38,9 @@ constexpr uint32_t kFloor2 = 0x80008000u; // packed (INT16_MIN, INT16_MIN): the 
 // at k * gaplessChunkBytes() + c * 256, hence (1) the bank of an access depends only on (copy, g): every
 // ds_read_b128 is conflict free by construction, and (2) the byte address of a row is (c << 8) | laneOffset with
 // laneOffset < 256, which one v_perm_b32 assembles from the packed residue word.
+// HALVES (two queries per register, 16 lanes per target): lane g (0..15) owns rows [g*R, g*R+R) of both queries, register r packs row
+// g*R + r of query A (low half) and of query B (high half); a bank row holds ONE copy of 16 lanes x 16 B at laneOffset = g * 16.  Each of the
+// four lane groups a ds_read_b128 is serviced in ({0-3, 12-15, 20-27}, ...) takes every g once: conflict free again, same image size.
 // ------------------------------------------------------------------------------------------------------------
 __host__ __device__ constexpr int gaplessChunkBytes() { return (kAlphabet + 1) * 256; }
 __host__ __device__ constexpr int gaplessChunks(int R) { return (R + 3) / 4; }

@@ -133,19 +133,34 @@ static int gaplessItems(fsgpu_ctx *ctx, int ov, const uint4 **items, uint32_t *n
 // ------------------------------------------------------------------------------------------------------------
 // gapless scan
 // ------------------------------------------------------------------------------------------------------------
-template <int R, bool TILED, bool PAIRED = false>
-static int launchGapless(fsgpu_ctx *ctx, const GaplessArgs &gaIn) {
-    GaplessArgs ga = gaIn;
+// once per thread and device: the dynamic-LDS attribute of an instantiation and the workgroups of it a CU holds
+template <int R, bool TILED, bool PAIRED, bool HALVES>
+static int prepareGapless(fsgpu_ctx *ctx, int *perCU) {
     const int lds = gaplessLdsBytes(R);
     static thread_local uint64_t attrDevs = 0;       // devices on which this thread has set the attribute (it is per device)
     static thread_local int perCUcached = 0;
     const uint64_t devBit = 1ull << (ctx->device & 63);
     if (!(attrDevs & devBit)) {
-        HIPCHK(hipFuncSetAttribute((const void *) k_gapless<R, TILED, PAIRED>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCUcached, k_gapless<R, TILED, PAIRED>, gaplessBlockThreads(R), lds));
+        HIPCHK(hipFuncSetAttribute((const void *) k_gapless<R, TILED, PAIRED, HALVES>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCUcached, k_gapless<R, TILED, PAIRED, HALVES>, gaplessBlockThreads(R), lds));
         attrDevs |= devBit;
     }
-    int perCU = perCUcached;
+    *perCU = perCUcached;
+    return FSGPU_OK;
+}
+
+template <int R, bool TILED, bool PAIRED = false, bool HALVES = false>
+static int launchGapless(fsgpu_ctx *ctx, const GaplessArgs &gaIn) {
+    GaplessArgs ga = gaIn;
+    const int lds = gaplessLdsBytes(R);
+    int perCU = 0, rc;
+    if ((rc = prepareGapless<R, TILED, PAIRED, HALVES>(ctx, &perCU)) != FSGPU_OK) return rc;
+    // A class's two-queries-per-register kernel is made ready with its unpaired one: whoever has run one query of a class alone (a warm-up)
+    // does not pay the set-up of the other inside the first batch that pairs the class
+    if constexpr (!TILED && !PAIRED && !HALVES && R >= kGaplessHalvesMinR && R <= kGaplessHalvesMaxR) {
+        int other = 0;
+        if ((rc = prepareGapless<R, false, false, true>(ctx, &other)) != FSGPU_OK) return rc;
+    }
     // Workgroups of 4 waves, each with its own LDS image; 3 per CU (12 waves, <= 135 KB LDS): more does not issue faster
     // (profiles/r01_q_gapless_ablation_ubench.txt, tools/bench_ab2.sh) and this leaves wave slots for the latency-bound SW
     // wavefront kernels of other in-flight queries to co-reside.  FSGPU_GAPLESS_BLOCKS_PER_CU overrides.
@@ -163,7 +178,7 @@ static int launchGapless(fsgpu_ctx *ctx, const GaplessArgs &gaIn) {
     // multi-query launch: ga.blocksPerQuery carries the number of queries on entry; every query gets `blocks` workgroups
     const uint32_t nQueries = ga.queries ? std::max(1u, ga.blocksPerQuery) : 1u;
     ga.blocksPerQuery = blocks;
-    hipLaunchKernelGGL((k_gapless<R, TILED, PAIRED>), dim3(blocks * nQueries), dim3(gaplessBlockThreads(R)), lds, ctx->stream, ga);
+    hipLaunchKernelGGL((k_gapless<R, TILED, PAIRED, HALVES>), dim3(blocks * nQueries), dim3(gaplessBlockThreads(R)), lds, ctx->stream, ga);
     HIPCHK(hipGetLastError());
     return FSGPU_OK;
 }
@@ -178,7 +193,12 @@ static const GaplessLaunchFn kGaplessUntiled[kGaplessMaxRUntiled + 1] = {nullptr
 static const GaplessLaunchFn kGaplessTiled[16] = {FS_GAPLESS8(1, 16, true), FS_GAPLESS8(1, 24, true)};
 // two short queries of class R = 1..16 in one kernel of 2 R registers
 static const GaplessLaunchFn kGaplessPaired[kGaplessMaxR / 2 + 1] = {nullptr, FS_GAPLESS8(2, 0, false, true), FS_GAPLESS8(2, 8, false, true)};
+// two queries of class R = 17..36 in the halves of every register, R registers
+static const GaplessLaunchFn kGaplessHalves[kGaplessHalvesMaxR - kGaplessHalvesMinR + 1] = {FS_GAPLESS8(1, 16, false, false, true), FS_GAPLESS8(1, 24, false, false, true),
+                                                                                           launchGapless<33, false, false, true>, launchGapless<34, false, false, true>,
+                                                                                           launchGapless<35, false, false, true>, launchGapless<36, false, false, true>};
 #undef FS_GAPLESS8
+static_assert(kGaplessHalvesMinR == 17 && kGaplessHalvesMaxR == 36, "kGaplessHalves lists the classes 17..36");
 
 // hits in the reference's order (hit_t::compareHitsByScoreAndId; scores are non-negative here)
 static void emitHits(fsgpu_hit *out, const uint32_t *ids, const int32_t *scores, uint32_t m) {
@@ -195,8 +215,8 @@ struct MqBatch {
     uint32_t n, nChunks, K;
     uint64_t scoreStride;
     std::vector<size_t> pOff;                // byte offset of slot k's PSSM in mqPssm
-    size_t nRec;                             // GaplessQuery records: one per slot, then one per pair of short queries
-    struct PairLaunch { int Rq; size_t rec0; int count; };
+    size_t nRec;                             // GaplessQuery records: one per slot, then one per pair of queries
+    struct PairLaunch { int Rq; size_t rec0; int count; bool halves; };      // halves: k_gapless HALVES of class Rq, else PAIRED of the short class Rq
     std::vector<PairLaunch> pairLaunches;
     std::vector<char> isPaired;
     int classOf(int k) const { return std::max(1, (q[batch[k]].L + 15) / 16); }
@@ -210,7 +230,8 @@ static int mqSlots(fsgpu_ctx *ctx, MqBatch &b) {
     int rc;
     b.pOff.assign(nb + 1, 0);
     for (int k = 0; k < nb; k++) b.pOff[k + 1] = b.pOff[k] + ((size_t) kAlphabet * b.q[b.batch[k]].L + 63) / 64 * 64;
-    const size_t nRecMax = (size_t) nb + (size_t) nb / 2 + 1;          // one record per query + one per pair of short queries
+    // one record per query + one per pair; a class of pairHalves may add a record whose B is dead
+    const size_t nRecMax = (size_t) nb + (size_t) nb / 2 + 1 + (kGaplessHalvesMaxR - kGaplessHalvesMinR + 1);
     if ((rc = ensureAll(ctx, {{ctx->mqPssm, b.pOff[nb]}, {ctx->mqScores, b.scoreStride * nb}, {ctx->mqQueues, nRecMax * 4}, {ctx->mqRec, nRecMax * sizeof(GaplessQuery)},
                               {ctx->mqHist, (size_t) nb * nChunks * 256 * 4}, {ctx->mqBaseGt, (size_t) nb * nChunks * 4}, {ctx->mqBaseTie, (size_t) nb * nChunks * 4},
                               {ctx->mqMeta, (size_t) nb * sizeof(SelMeta)}, {ctx->mqOutId, (size_t) nb * K * 4}, {ctx->mqOutScore, (size_t) nb * K * 4}, {ctx->mqIdent, (size_t) nb * 8}})) != FSGPU_OK) return rc;
@@ -235,8 +256,77 @@ static int mqSlots(fsgpu_ctx *ctx, MqBatch &b) {
     return FSGPU_OK;
 }
 
+// ------------------------------------------------------------------------------------------------------------
+// Which queries of a call share the registers of k_gapless<R, false, false, HALVES> (classes kGaplessHalvesMinR .. kGaplessHalvesMaxR).
+// cls[i] = register class of query i.  Per query: launchClass = the class whose launch carries it, record = its record in that launch and
+// half = 0 (query A, low halves) or 1 (query B); record = half = -1: not placed here, the query runs as it did (unpaired kernel, paired
+// short classes, row tiles).
+//   * a class with one member keeps the unpaired kernel; one with m >= 2 members gets ONE launch over its members two by two, in order;
+//   * the odd member out of a class of m >= 3 would run with a dead B, which costs what a whole query costs: it may move up instead, at most
+//     kGaplessHalvesPromote registers, as query B beside the odd member out of a class that has one, or beside a single member (whose launch
+//     then is one record of this kernel).  Every class keeps its one launch: nobody leaves a class of fewer than three, no launch is added.
+//     The guest's profile is zero behind its length like any query's and the larger class's column segments warm up longer than it needs:
+//     its scores are those of its own class.  Who moves where is chosen for the fewest dead halves (a small dynamic program over the
+//     classes: two odd members out that meet save two, a guest of a single member one).
+// Pure host function, exported as fsgpu_gapless_pair_halves for the CPU tests.  Returns the number of records.
+// ------------------------------------------------------------------------------------------------------------
+static int pairHalves(const int *cls, int n, int *launchClass, int *record, int *half) {
+    int members[kGaplessHalvesMaxR + 1] = {0}, placed[kGaplessHalvesMaxR + 1] = {0}, last[kGaplessHalvesMaxR + 1];
+    const auto inRange = [](int R) { return R >= kGaplessHalvesMinR && R <= kGaplessHalvesMaxR; };
+    for (int i = 0; i < n; i++)
+        if (inRange(cls[i])) members[cls[i]]++;
+    int records = 0;
+    for (int i = 0; i < n; i++) {
+        launchClass[i] = cls[i]; record[i] = -1; half[i] = -1;
+        if (!inRange(cls[i])) continue;
+        last[cls[i]] = i;
+        if (members[cls[i]] < 2) continue;
+        const int p = placed[cls[i]]++;
+        record[i] = p / 2; half[i] = p % 2;
+        if (half[i] == 0) records++;
+    }
+    // Fewest dead halves: dead[R][s] = those from class R on when the odd members out of R - 2 (s & 1) and R - 1 (s & 2) still look for a seat.
+    // At R the one from R - 2 is seated or lost; a class that seats nobody and has an odd member out of its own (m >= 3) hands it on.
+    static_assert(kGaplessHalvesPromote == 2, "the state below holds the two classes in reach");
+    constexpr int N = kGaplessHalvesMaxR + 2;
+    int dead[N + 1][4], take[N + 1][4];               // take: 0 nobody, 1 the one from R - 2, 2 the one from R - 1
+    for (int s = 0; s < 4; s++) dead[N][s] = (s & 1) + (s >> 1);
+    for (int R = N - 1; R >= kGaplessHalvesMinR; R--)
+        for (int s = 0; s < 4; s++) {
+            const int m = R <= kGaplessHalvesMaxR ? members[R] : 0;
+            dead[R][s] = 1 << 30;
+            for (int t = 1; t <= 3; t++) {            // seating first: with equal dead halves a shared record is the cheaper one
+                const int who = t % 3;
+                if (who && (m % 2 == 0 || !(s & who))) continue;
+                const int left = s & ~who;
+                const int mine = (m >= 3 && m % 2 == 1 && !who) ? 2 : 0;
+                const int d = (left & 1) + dead[R + 1][(left >> 1) | mine];
+                if (d < dead[R][s]) { dead[R][s] = d; take[R][s] = who; }
+            }
+        }
+    for (int R = kGaplessHalvesMinR, s = 0; R <= kGaplessHalvesMaxR; R++) {
+        const int who = take[R][s], m = members[R];
+        if (who) {
+            const int i = last[R - (who == 1 ? 2 : 1)];                    // that class's odd member out: B of this class's last record
+            if (m >= 3) records--;                                           // the two odd members out share a record
+            else { record[last[R]] = 0; half[last[R]] = 0; }                // a single member opens its class's only record
+            launchClass[i] = R; record[i] = m / 2; half[i] = 1;
+        }
+        s = ((s & ~who) >> 1) | ((m >= 3 && m % 2 == 1 && !who) ? 2 : 0);
+    }
+    return records;
+}
+
+extern "C" int fsgpu_gapless_pair_halves(const int32_t *classes, int n, int32_t *launchClass, int32_t *record, int32_t *half) {
+    if (n < 0 || (n > 0 && (!classes || !launchClass || !record || !half))) return -1;
+    for (int i = 0; i < n; i++)
+        if (classes[i] < 1) return -1;
+    return pairHalves(classes, n, launchClass, record, half);
+}
+
 // Short queries (<= 256 residues) of one 16-row class run two to a kernel (k_gapless<2R, false, PAIRED>: the per-column
-// instructions that do not scale with the rows are shared); an odd one out runs alone.
+// instructions that do not scale with the rows are shared); an odd one out runs alone.  Queries of the classes 17 .. 36 share registers
+// instead (pairHalves).
 static void mqPairShort(fsgpu_ctx *ctx, MqBatch &b) {
     // classes up to 16 registers (256 residues): beyond that the pair would need the 8-wave workgroups of R > 36, which was measured
     // and loses (pairs up to class 20 / 24 / 28 at 1M targets: 2.74 / 2.77 / 2.84 ms per query against 2.76 without)
@@ -246,7 +336,7 @@ static void mqPairShort(fsgpu_ctx *ctx, MqBatch &b) {
     for (int k0 = 0; k0 < b.nb;) {
         const int R = b.classOf(k0), k1 = b.classEnd(k0);
         if (R <= pairMaxR && k1 - k0 >= 2) {
-            MqBatch::PairLaunch pl{R, b.nRec, (k1 - k0) / 2};
+            MqBatch::PairLaunch pl{R, b.nRec, (k1 - k0) / 2, false};
             for (int p2 = 0; p2 < pl.count; p2++) {
                 const int ka = k0 + 2 * p2, kb = ka + 1;
                 rec[b.nRec] = rec[ka];
@@ -259,6 +349,32 @@ static void mqPairShort(fsgpu_ctx *ctx, MqBatch &b) {
         }
         k0 = k1;
     }
+    // classes 17 .. 36: two queries in the halves of every register (pairHalves), one launch per class
+    std::vector<int> cls(b.nb), launchClass(b.nb), record(b.nb), half(b.nb);
+    for (int k = 0; k < b.nb; k++) cls[k] = b.classOf(k);
+    if (pairHalves(cls.data(), b.nb, launchClass.data(), record.data(), half.data()) == 0) return;
+    int count[kGaplessHalvesMaxR + 1] = {0};
+    for (int k = 0; k < b.nb; k++)
+        if (record[k] >= 0) count[launchClass[k]] = std::max(count[launchClass[k]], record[k] + 1);
+    size_t rec0[kGaplessHalvesMaxR + 1] = {0};
+    for (int R = kGaplessHalvesMaxR; R >= kGaplessHalvesMinR; R--) {           // long classes first, like the unpaired launches
+        if (!count[R]) continue;
+        rec0[R] = b.nRec;
+        b.pairLaunches.push_back(MqBatch::PairLaunch{R, b.nRec, count[R], true});
+        b.nRec += (size_t) count[R];
+    }
+    for (int pass = 0; pass < 2; pass++)                  // every record's A first: it brings the record's own queue word and a B that is absent
+        for (int k = 0; k < b.nb; k++) {
+            if (record[k] < 0 || half[k] != pass) continue;
+            const size_t at = rec0[launchClass[k]] + (size_t) record[k];
+            if (pass == 0) {
+                rec[at] = rec[k];
+                rec[at].queue = (uint32_t *) ctx->mqQueues.p + at;
+            } else {
+                rec[at].pssmB = rec[k].pssm; rec[at].scoresB = rec[k].scores; rec[at].LB = rec[k].L; rec[at].capB = rec[k].cap;
+            }
+            b.isPaired[k] = 1;
+        }
 }
 
 static int mqUpload(fsgpu_ctx *ctx, const MqBatch &b) {
@@ -306,7 +422,7 @@ static int mqScan(fsgpu_ctx *ctx, const MqBatch &b) {
         k0 = k1;
     }
     for (const MqBatch::PairLaunch &pl : b.pairLaunches) {
-        Launch l{kGaplessPaired[pl.Rq], nullptr, 0, pl.rec0, pl.count};
+        Launch l{pl.halves ? kGaplessHalves[pl.Rq - kGaplessHalvesMinR] : kGaplessPaired[pl.Rq], nullptr, 0, pl.rec0, pl.count};
         if ((rc = gaplessItems(ctx, pl.Rq, &l.items, &l.nItems, &clear)) != FSGPU_OK) return rc;     // warm-up of a column segment = the QUERY's rows
         anyClear = anyClear || clear;                     // (the loop above has asked for every class already, paired or not; kept so that this does not depend on it)
         launches.push_back(l);

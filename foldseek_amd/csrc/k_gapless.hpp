@@ -112,7 +112,7 @@ struct GaplessArgs {
 // is dead after the next hand-off anyway), kFoldBoth folds it together with the one kept by the column before -- one max3 per two columns.
 // TILED: bi / bo = the chunk's border words in and out, carryPrev = the border value of the column before the chunk.
 enum { kFoldAlone = 0, kFoldKeep = 1, kFoldBoth = 2 };
-template <int R, bool TILED, bool PAIRED, bool ROLLED>
+template <int R, bool TILED, bool PAIRED, bool ROLLED, bool HALVES = false>
 __device__ __forceinline__ void gaplessColumn(uint32_t (&S)[R], uint32_t &M, uint32_t &M2, uint32_t &kept, const uint32_t word, const int b, const int fold,
                                               const uint32_t laneOff, const uint32_t sel, const int g, const uint32_t carryPrev, const uint32_t (&bi)[8], uint32_t (&bo)[8]) {
     constexpr int CHB = gaplessChunkBytes();
@@ -151,7 +151,9 @@ __device__ __forceinline__ void gaplessColumn(uint32_t (&S)[R], uint32_t &M, uin
         const uint32_t fromTile = (b == 0) ? carryPrev : ((b & 1) ? (bi[(b - 1) >> 1] & 0xffffu) : (bi[(b - 1) >> 1] >> 16));
         prev = (g == 0) ? (fromTile << 16) : prev;
     }
-    const uint32_t in = __builtin_amdgcn_perm(prev, S[R - 1], sel);
+    // HALVES: both halves of a register belong to the rows of ONE lane (two queries), so both move on to the next lane and the dpp move is the
+    // whole hand-off; bound_ctrl hands the first lane of a 16-lane row -- of a target group -- the zero both queries' diagonals start from
+    const uint32_t in = HALVES ? prev : __builtin_amdgcn_perm(prev, S[R - 1], sel);
     if constexpr (readsFirst) {
 #pragma unroll
         for (int r = R - 1; r >= 1; r--) S[r] = pk_addc_f16(S[r - 1], P[r]);
@@ -195,10 +197,20 @@ __device__ __forceinline__ void gaplessColumn(uint32_t (&S)[R], uint32_t &M, uin
 // 0 .. 8R-1), query B in lanes 4..7 -- so the 3 per-column instructions that do not depend on R are paid once for both: a query of
 // 128 residues runs with R = 16 registers per lane instead of 8, 11 % instead of 20 % of the column's instructions are overhead.
 // Lane 4 starts B's diagonals at zero exactly like lane 0 starts A's; the final maximum is taken over 4 lanes per query.
-template <int R, bool TILED, bool PAIRED = false>
+//
+// HALVES: two queries of one class of 17 .. 36 registers share every REGISTER -- lane g = 0..15 of a target group owns rows [g R, (g + 1) R) of
+// both, row g R + r of query A in the low half of register r and the same row of query B in the high half, scored against the same target.
+// Nothing crosses from one half to the other any more: the hand-off is the bare v_mov_b32_dpp (gaplessColumn), 1.5 R + 2 instructions per column
+// and lane for the same 2 R cells.  R, the LDS image (16 lanes x 16 B fill a bank row once; the four 16-lane groups a ds_read_b128 is serviced in
+// each see 16 different slots) and the resident workgroups are those of the class.  A target group is a dpp row, a wave holds four targets: it
+// runs an item's columns once for the stripe's slots 0..3 and once for 4..7 (the second read of the lines hits L2).  A query B that is shorter
+// than the class (pairHalves, fsgpu_gapless.hip, may bring one up from two classes below) simply has zero rows behind its length, like A; a record without a
+// B carries the dead value in every high half.
+template <int R, bool TILED, bool PAIRED = false, bool HALVES = false>
 __global__ __launch_bounds__(gaplessBlockThreads(R)) void k_gapless(GaplessArgs a) {
     static_assert(R >= 1 && R <= (TILED ? kGaplessMaxR : kGaplessMaxRUntiled), "register count out of range");
     static_assert(!PAIRED || (!TILED && R % 2 == 0), "paired queries: untiled, even register count");
+    static_assert(!HALVES || (!TILED && !PAIRED && R >= kGaplessHalvesMinR && R <= kGaplessHalvesMaxR), "two queries per register: untiled, the 4-wave classes beyond the paired ones");
     constexpr int BLOCK = gaplessBlockThreads(R);
     constexpr int CHB = gaplessChunkBytes();
     constexpr int NCH = gaplessChunks(R);         // ds_read_b128 per column; the last one may carry unused registers
@@ -212,14 +224,40 @@ __global__ __launch_bounds__(gaplessBlockThreads(R)) void k_gapless(GaplessArgs 
         blocksOfQuery = a.blocksPerQuery;
         const GaplessQuery gq = a.queries[qi];
         a.pssm = gq.pssm; a.scores = gq.scores; a.queue = gq.queue; a.L = gq.L; a.cap = gq.cap;
-        if constexpr (PAIRED) { pssmB = gq.pssmB; scoresB = gq.scoresB; LB = gq.LB; capB = gq.capB; }
+        if constexpr (PAIRED || HALVES) { pssmB = gq.pssmB; scoresB = gq.scoresB; LB = gq.LB; capB = gq.capB; }
     }
 
     // ---- build the LDS image from the int8 pssm (once per workgroup) ----
     // One item = (profile row, lane g, 4-register chunk k): 4 + 4 profile bytes -> one 16-byte slot, stored to both
     // copies.  All byte loads of an item are independent and the item loop is unrolled, so the build costs a couple of
     // global round trips instead of one per dword.
-    {
+    if constexpr (HALVES) {
+        // one item = (profile row, lane g of 16, chunk k): 4 bytes of A and 4 of B -> one 16-byte slot of the single copy
+        const int L = a.L;
+        constexpr int nItems = (kAlphabet + 1) * 16 * NCH;
+        constexpr int nIter = (nItems + BLOCK - 1) / BLOCK;
+#pragma unroll
+        for (int it = 0; it < nIter; it++) {
+            const int idx = it * BLOCK + threadIdx.x;
+            if (idx < nItems) {
+                const int g = idx & 15, k = (idx >> 4) % NCH, row = (idx >> 4) / NCH;
+                uint32_t v[4];
+#pragma unroll
+                for (int w = 0; w < 4; w++) {
+                    const int r = 4 * k + w;
+                    const int qr = g * R + r;
+                    if (row == kDeadCode || r >= R) {
+                        v[w] = kDead2;
+                    } else {
+                        const int lo = qr < L ? (int) a.pssm[row * L + qr] : 0;
+                        const uint32_t hi = !pssmB ? (kDead2 >> 16) : f16ScaledBits(qr < LB ? (int) pssmB[row * LB + qr] : 0);
+                        v[w] = f16ScaledBits(lo) | (hi << 16);
+                    }
+                }
+                *(u32x4 *) (smem + k * CHB + row * 256 + g * 16) = (u32x4){v[0], v[1], v[2], v[3]};
+            }
+        }
+    } else {
         const int L = a.L;
         constexpr int nItems = (kAlphabet + 1) * 8 * NCH;
         constexpr int nIter = (nItems + BLOCK - 1) / BLOCK;
@@ -255,9 +293,9 @@ __global__ __launch_bounds__(gaplessBlockThreads(R)) void k_gapless(GaplessArgs 
     __syncthreads();
 
     const int lane = threadIdx.x & 63;
-    const int j = lane >> 3;          // target slot inside the stripe
-    const int g = lane & 7;           // lane inside the target group
-    const uint32_t laneOff = (uint32_t) (((j >> 1) & 1) * 128 + g * 16);       // < 256: fits the low address byte
+    const int j0 = HALVES ? lane >> 4 : lane >> 3;          // target slot inside the stripe (HALVES: of the first pass, the second runs slot j0 + 4)
+    const int g = HALVES ? lane & 15 : lane & 7;            // lane inside the target group
+    const uint32_t laneOff = (uint32_t) (HALVES ? g * 16 : ((j0 >> 1) & 1) * 128 + g * 16);       // < 256: fits the low address byte
     // v_perm selector for the hand-off: lo half <- hi half of the previous lane's last register,
     // hi half <- lo half of my own last register.  {S0 = prev (bytes 4..7), S1 = own (bytes 0..3)}.
     // First lane of a target group (untiled): lo half <- constant zero (selector byte 0x0c), so the value the dpp
@@ -277,82 +315,83 @@ __global__ __launch_bounds__(gaplessBlockThreads(R)) void k_gapless(GaplessArgs 
         const uint64_t soff = ((uint64_t) (item.w & 0x00ffffffu) << 32) | item.z;       // every record carries the trim in the top byte, whoever reads it
         // real columns of the stripe's last chunk where they are fewer than 16 (wave-uniform, 0 = every chunk of the item is full)
         const uint32_t tail = TILED ? 0u : (item.w >> 24) & 15u;
-        const uint4 *src = a.scan + soff + j;
-        // border arrays use the scan layout at 2 bytes per residue: 32 bytes per (chunk, target)
-        const uint4 *bin = TILED ? (const uint4 *) a.borderIn + (soff + j) * 2 : nullptr;
-        uint4 *bout = TILED ? (uint4 *) a.borderOut + (soff + j) * 2 : nullptr;
-        uint32_t carryPrevChunk = 0;                      // border value of the column before this chunk
-
-        uint32_t S[R];
-        uint32_t M = 0, M2 = 0;                           // two running maxima: no dependent max3 chain
-#pragma unroll
-        for (int r = 0; r < R; r++) S[r] = 0;
-
-        uint32_t kept = 0;                                // odd R: the last register of an even column, see gaplessColumn
-        uint4 nxt = src[(size_t) cBegin * 8];
-        const uint32_t cFull = tail ? cEnd - 1 : cEnd;    // chunks that run all 16 columns
-        for (uint32_t c = cBegin; c < cFull; c++) {
-            const uint4 cur = nxt;
-            if (c + 1 < cEnd) nxt = src[(size_t) (c + 1) * 8];
-            const uint32_t words[4] = {cur.x, cur.y, cur.z, cur.w};
-            uint32_t bi[8], bo[8];
-            if constexpr (TILED) {
-                if (!a.firstTile && g == 0) {
-                    const uint4 x0 = bin[(size_t) c * 16], x1 = bin[(size_t) c * 16 + 1];
-                    bi[0] = x0.x; bi[1] = x0.y; bi[2] = x0.z; bi[3] = x0.w; bi[4] = x1.x; bi[5] = x1.y; bi[6] = x1.z; bi[7] = x1.w;
-                } else {
-#pragma unroll
-                    for (int k = 0; k < 8; k++) bi[k] = 0;
-                }
-#pragma unroll
-                for (int k = 0; k < 8; k++) bo[k] = 0;
-            }
-#pragma unroll
-            for (int b = 0; b < 16; b++)
-                gaplessColumn<R, TILED, PAIRED, false>(S, M, M2, kept, words[b >> 2], b, TILED ? kFoldAlone : (b & 1) ? kFoldBoth : kFoldKeep, laneOff, sel, g, carryPrevChunk, bi, bo);
-            if constexpr (TILED) {
-                carryPrevChunk = bi[7] >> 16;
-                if (!a.lastTile && g == 7) {
-                    bout[(size_t) c * 16] = make_uint4(bo[0], bo[1], bo[2], bo[3]);
-                    bout[(size_t) c * 16 + 1] = make_uint4(bo[4], bo[5], bo[6], bo[7]);
-                }
-            }
+        // HALVES: the ids of the targets of both passes, asked for beside the first chunk so that neither pass waits for its own
+        uint32_t tidPass0 = 0, tidPass1 = 0;
+        if constexpr (HALVES) {
+            tidPass0 = a.stripeTargets[stripe * kStripeTargets + j0];
+            tidPass1 = a.stripeTargets[stripe * kStripeTargets + j0 + 4];
         }
-        if constexpr (!TILED) {
-            // The stripe's last chunk (already loaded: nxt) holds `tail` real columns; the rest is the dead code, whose cells are zero and
-            // feed nothing.  The same column body once more, in a loop with a scalar trip count: the codes move down through the four
-            // words, so that every round finds its column in the low byte of the first.
-            if (tail) {
-                uint32_t w0 = nxt.x, w1 = nxt.y, w2 = nxt.z, w3 = nxt.w;
-                uint32_t none[8];
-                for (uint32_t t = 0; t < tail; t++) {
-                    gaplessColumn<R, TILED, PAIRED, true>(S, M, M2, kept, w0, 0, kFoldAlone, laneOff, sel, g, 0u, none, none);
-                    w0 = __builtin_amdgcn_alignbit(w1, w0, 8); w1 = __builtin_amdgcn_alignbit(w2, w1, 8);
-                    w2 = __builtin_amdgcn_alignbit(w3, w2, 8); w3 >>= 8;
+#pragma unroll 1
+        for (int h = 0; h < (HALVES ? 2 : 1); h++) {       // HALVES: stripe slots 0..3, then 4..7; everything from S to the stores once per pass
+            const int j = j0 + 4 * h;
+            const uint32_t tidHalves = h ? tidPass1 : tidPass0;
+            if constexpr (HALVES) {
+                if (__ballot(tidHalves < a.nTargets) == 0) continue;          // four empty slots (wave-uniform)
+            }
+            const uint4 *src = a.scan + soff + j;
+            // border arrays use the scan layout at 2 bytes per residue: 32 bytes per (chunk, target)
+            const uint4 *bin = TILED ? (const uint4 *) a.borderIn + (soff + j) * 2 : nullptr;
+            uint4 *bout = TILED ? (uint4 *) a.borderOut + (soff + j) * 2 : nullptr;
+            uint32_t carryPrevChunk = 0;                      // border value of the column before this chunk
+
+            uint32_t S[R];
+            uint32_t M = 0, M2 = 0;                           // two running maxima: no dependent max3 chain
+#pragma unroll
+            for (int r = 0; r < R; r++) S[r] = 0;
+
+            uint32_t kept = 0;                                // odd R: the last register of an even column, see gaplessColumn
+            uint4 nxt = src[(size_t) cBegin * 8];
+            const uint32_t cFull = tail ? cEnd - 1 : cEnd;    // chunks that run all 16 columns
+            for (uint32_t c = cBegin; c < cFull; c++) {
+                const uint4 cur = nxt;
+                if (c + 1 < cEnd) nxt = src[(size_t) (c + 1) * 8];
+                const uint32_t words[4] = {cur.x, cur.y, cur.z, cur.w};
+                uint32_t bi[8], bo[8];
+                if constexpr (TILED) {
+                    if (!a.firstTile && g == 0) {
+                        const uint4 x0 = bin[(size_t) c * 16], x1 = bin[(size_t) c * 16 + 1];
+                        bi[0] = x0.x; bi[1] = x0.y; bi[2] = x0.z; bi[3] = x0.w; bi[4] = x1.x; bi[5] = x1.y; bi[6] = x1.z; bi[7] = x1.w;
+                    } else {
+#pragma unroll
+                        for (int k = 0; k < 8; k++) bi[k] = 0;
+                    }
+#pragma unroll
+                    for (int k = 0; k < 8; k++) bo[k] = 0;
+                }
+#pragma unroll
+                for (int b = 0; b < 16; b++)
+                    gaplessColumn<R, TILED, PAIRED, false, HALVES>(S, M, M2, kept, words[b >> 2], b, TILED ? kFoldAlone : (b & 1) ? kFoldBoth : kFoldKeep, laneOff, sel, g, carryPrevChunk, bi, bo);
+                if constexpr (TILED) {
+                    carryPrevChunk = bi[7] >> 16;
+                    if (!a.lastTile && g == 7) {
+                        bout[(size_t) c * 16] = make_uint4(bo[0], bo[1], bo[2], bo[3]);
+                        bout[(size_t) c * 16 + 1] = make_uint4(bo[4], bo[5], bo[6], bo[7]);
+                    }
                 }
             }
-        }
-        // max over both strips and the 8 lanes of the group; non-negative FP16 values order like their bit patterns
-        M = pk_max3_f16(M, M2, M2);
-        int m = max((int) (M & 0xffff), (int) (M >> 16));
-        m = max(m, __shfl_xor(m, 1));
-        m = max(m, __shfl_xor(m, 2));
-        if constexpr (!PAIRED) m = max(m, __shfl_xor(m, 4));
-        const uint32_t tid = a.stripeTargets[stripe * kStripeTargets + j];
-        if constexpr (PAIRED) { if (g == 4) { a.scores = scoresB; a.cap = capB; } }       // lane 4 reports query B
-        if ((g == 0 || (PAIRED && g == 4)) && tid < a.nTargets) {
-            if constexpr (TILED) {
-                if (!a.firstTile) m = max(m, (int) a.scoreAcc[tid]);
-                if (!a.lastTile) a.scoreAcc[tid] = (int16_t) m;
+            if constexpr (!TILED) {
+                // The stripe's last chunk (already loaded: nxt) holds `tail` real columns; the rest is the dead code, whose cells are zero and
+                // feed nothing.  The same column body once more, in a loop with a scalar trip count: the codes move down through the four
+                // words, so that every round finds its column in the low byte of the first.
+                if (tail) {
+                    uint32_t w0 = nxt.x, w1 = nxt.y, w2 = nxt.z, w3 = nxt.w;
+                    uint32_t none[8];
+                    for (uint32_t t = 0; t < tail; t++) {
+                        gaplessColumn<R, TILED, PAIRED, true, HALVES>(S, M, M2, kept, w0, 0, kFoldAlone, laneOff, sel, g, 0u, none, none);
+                        w0 = __builtin_amdgcn_alignbit(w1, w0, 8); w1 = __builtin_amdgcn_alignbit(w2, w1, 8);
+                        w2 = __builtin_amdgcn_alignbit(w3, w2, 8); w3 >>= 8;
+                    }
+                }
             }
-            if (!TILED || a.lastTile) {
-                int sc = (int) (__half2float(__ushort_as_half((unsigned short) m)) * 2048.0f + 0.5f);
-                sc = sc < a.cap ? sc : a.cap;
+            // the score of target tid, from the FP16 bits of its maximum: cut to the query's cap, stored into the query's slice
+            const auto putScore = [&](uint8_t *scores, const int cap, const uint32_t tid, const int mBits) __attribute__((always_inline)) {
+                int sc = (int) (__half2float(__ushort_as_half((unsigned short) mBits)) * 2048.0f + 0.5f);
+                sc = sc < cap ? sc : cap;
                 if (!split) {
-                    a.scores[tid] = (uint8_t) sc;
+                    scores[tid] = (uint8_t) sc;
                 } else {
                     // column segment: byte-wise maximum into the (zeroed) score array
-                    uint32_t *word = (uint32_t *) (a.scores + (tid & ~3u));
+                    uint32_t *word = (uint32_t *) (scores + (tid & ~3u));
                     const int sh = (int) (tid & 3u) * 8;
                     uint32_t old = *word;
                     while ((int) ((old >> sh) & 0xffu) < sc) {
@@ -361,6 +400,34 @@ __global__ __launch_bounds__(gaplessBlockThreads(R)) void k_gapless(GaplessArgs 
                         if (seen == old) break;
                         old = seen;
                     }
+                }
+            };
+            M = pk_max3_f16(M, M2, M2);
+            if constexpr (HALVES) {
+                // max over the 16 lanes of the group, query A in the low halves and query B in the high ones: non-negative FP16 values order
+                // like their bit patterns, so one packed integer maximum serves both
+                M = pk_max_i16(M, (uint32_t) __shfl_xor((int) M, 1));
+                M = pk_max_i16(M, (uint32_t) __shfl_xor((int) M, 2));
+                M = pk_max_i16(M, (uint32_t) __shfl_xor((int) M, 4));
+                M = pk_max_i16(M, (uint32_t) __shfl_xor((int) M, 8));
+                if (g == 0 && tidHalves < a.nTargets) {
+                    putScore(a.scores, a.cap, tidHalves, (int) (M & 0xffff));
+                    if (scoresB) putScore(scoresB, capB, tidHalves, (int) (M >> 16));
+                }
+            } else {
+                // max over both strips and the 8 lanes of the group; non-negative FP16 values order like their bit patterns
+                int m = max((int) (M & 0xffff), (int) (M >> 16));
+                m = max(m, __shfl_xor(m, 1));
+                m = max(m, __shfl_xor(m, 2));
+                if constexpr (!PAIRED) m = max(m, __shfl_xor(m, 4));
+                const uint32_t tid = a.stripeTargets[stripe * kStripeTargets + j];
+                if constexpr (PAIRED) { if (g == 4) { a.scores = scoresB; a.cap = capB; } }       // lane 4 reports query B
+                if ((g == 0 || (PAIRED && g == 4)) && tid < a.nTargets) {
+                    if constexpr (TILED) {
+                        if (!a.firstTile) m = max(m, (int) a.scoreAcc[tid]);
+                        if (!a.lastTile) a.scoreAcc[tid] = (int16_t) m;
+                    }
+                    if (!TILED || a.lastTile) putScore(a.scores, a.cap, tid, m);
                 }
             }
         }

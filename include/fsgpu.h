@@ -185,6 +185,14 @@ int64_t fsgpu_gapless_plan_items(const uint32_t *stripeLen, uint32_t nStripes, i
  * chunk, 0 for every other.  Returns nItems, or -1 for arguments that do not fit each other. */
 int64_t fsgpu_gapless_item_records(const uint64_t *items, uint64_t nItems, const uint32_t *stripeLen, const uint32_t *stripeCols,
                                    uint32_t nStripes, uint32_t *records);
+/* Host-only: which queries of one fsgpu_gapless_scan_multi call share registers in the classes 17 .. 36 (two queries in the halves of
+ * every register, 16 lanes a target).  classes[i] = ceil(L_i / 16) >= 1.  Per query: launchClass[i] = the class whose launch carries it,
+ * record[i] = its record in that launch, half[i] = 0 (query A) or 1 (query B); record = half = -1 and launchClass = its own class: the
+ * query is not placed here (a class with one member and no guest, the classes up to 16 and beyond 36).  A class with two or more members gets one launch
+ * over its members two by two; the odd member out of a class of three or more may move up, two registers at most, as query B beside the odd
+ * member out of another such class or beside a single member (that class's launch then is one record of this kind), chosen so that the
+ * fewest records run without a B.  Every class present keeps exactly one launch.  Returns the number of records, or -1 for a bad argument. */
+int fsgpu_gapless_pair_halves(const int32_t *classes, int n, int32_t *launchClass, int32_t *record, int32_t *half);
 int fsgpu_gapless_launch(fsgpu_ctx *ctx, const int8_t *pssm, int L, int scoreCap, int minScore,
                          int64_t identityId, int maxRes);
 int fsgpu_gapless_finish(fsgpu_ctx *ctx, fsgpu_hit *out, int *nout);

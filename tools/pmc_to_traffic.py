@@ -80,7 +80,9 @@ sw_entry(os.path.join(d, f"{tag}_pmc_bench_1M.json"), os.path.join(d, f"{tag}_pm
 sw_entry(os.path.join(d, f"{tag}_pmc_bench_1M_t2.json"), os.path.join(d, f"{tag}_pmc_bench_1M_t2_benchline.json"), "1000000:2", "pmc_bench_1M_t2_steps3.txt")
 sw_entry(os.path.join(d, f"{tag}_pmc_allvsall_200k.json"), os.path.join(d, f"{tag}_pmc_allvsall_200k_benchline.json"), "200000:2", "pmc_allvsall_200k.txt", allvsall=True)
 
-# --- k-mer prefilter: every kernel of one 32-query batch, per index hit
+# --- k-mer prefilter: every kernel of one 32-query batch, per index hit (a pass directory of the scan alone ends here)
+if not os.path.exists(os.path.join(d, f"{tag}_pmc_kmer_1M.json")):
+    sys.exit(0)
 k = json.load(open(os.path.join(d, f"{tag}_pmc_kmer_1M.json")))
 cnt = None
 for line in open(os.path.join(d, f"{tag}_pmc_kmer_1M_counts.txt")):
