@@ -208,6 +208,14 @@ def lib():
         "fsgpu_sw_multi_dir": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp]),
         "fsgpu_sw_multi_dir_c": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
         "fsgpu_sw_multi_c": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp]),
+        "fsgpu_sw_multi_dir_p": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp]),
+        "fsgpu_sw_multi_p": (i32, [vp, vp, i32, i32, i32, vp, vp]),
+        "fshost_profile_decode": (i32, [vp, C.c_size_t, vp, vp, vp, vp, C.c_char_p, C.c_size_t]),
+        "fshost_profile_bias": (i32, [vp, i32]),
+        "fshost_search_prefilter_profile": (i32, [vp, vp, i32, i64, vp]),
+        "fshost_search_prefilter_batch_profile": (i32, [vp, i32, vp, vp, vp, vp, vp]),
+        "fshost_search_align_profile": (i32, [vp, vp, i64, vp, i32, vp]),
+        "fshost_search_align_batch_profile": (i32, [vp, i32, vp, vp, vp, vp, vp, vp]),
         "fsgpu_sw_scan_c": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, u64, vp]),
         "fsgpu_sw_scan_last": (None, [vp, vp]),
         "fshost_search_backtrace": (C.c_char_p, [vp, vp]),
@@ -243,7 +251,7 @@ def lib():
 def exported_symbols():
     return ["fsgpu_create", "fsgpu_destroy", "fsgpu_last_error", "fsgpu_device", "fsgpu_stream", "fsgpu_db_load",
             "fsgpu_db_adopt_device", "fsgpu_db_check_table", "fsgpu_db_size", "fsgpu_db_residues", "fsgpu_gapless_scan", "fsgpu_gapless_scores",
-            "fsgpu_gapless_launch", "fsgpu_gapless_finish", "fsgpu_sw_batch", "fsgpu_sw_multi", "fsgpu_sw_multi_dir", "fsgpu_sw_multi_dir_c", "fsgpu_sw_multi_c", "fsgpu_sw_launch", "fsgpu_sw_finish",
+            "fsgpu_gapless_launch", "fsgpu_gapless_finish", "fsgpu_sw_batch", "fsgpu_sw_multi", "fsgpu_sw_multi_dir", "fsgpu_sw_multi_dir_c", "fsgpu_sw_multi_c", "fsgpu_sw_multi_dir_p", "fsgpu_sw_multi_p", "fsgpu_sw_launch", "fsgpu_sw_finish",
             "fsgpu_db_broadcast", "fsgpu_rccl_selfcheck", "fsgpu_device_count", "fsgpu_live_devices", "fsgpu_gapless_plan_items", "fsgpu_gapless_item_records", "fsgpu_gapless_pair_halves", "fsgpu_block_backtrace", "fsgpu_block_backtrace_footprint",
             "fsgpu_lddt_batch", "fsgpu_tm_batch", "fsgpu_tm_superpose_batch", "fsgpu_last_kernel_ms", "fsgpu_history_counters", "fsgpu_sw_last_passes", "fsgpu_sw3_last_plan", "fsgpu_kmer_index_build", "fsgpu_kmer_index_entries", "fsgpu_kmer_index_entry_bytes", "fsgpu_kmer_index_get_params", "fsgpu_kmer_search",
             "fsgpu_kmer_index_copy", "fsgpu_kmer_row_copy", "fsgpu_kmer_last_counts", "fsgpu_kmer_last_segments", "fsgpu_kmer_plan_coarse", "fsgpu_kmer_batch_hint",
@@ -648,6 +656,52 @@ class Context:
             rf.append(fwd[b:b + len(k[0])].copy()); rr.append(rev[b:b + len(k[0])].copy()); b += len(k[0])
         return rf, rr
 
+    def _pqueries(self, queries):
+        """fsgpu_sw_pquery array of (pAA_fwd|None, p3Di_fwd, pAA_rev|None, p3Di_rev, target_ids): int8 [21, L] tables"""
+        class Q(C.Structure):
+            _fields_ = [("pAA_fwd", C.c_void_p), ("p3Di_fwd", C.c_void_p), ("pAA_rev", C.c_void_p), ("p3Di_rev", C.c_void_p),
+                        ("L", C.c_int32), ("n", C.c_int32), ("targetIds", C.c_void_p)]
+        keep, arr = [], (Q * max(1, len(queries)))()
+        for i, (paf, p3f, par_, p3r, ids) in enumerate(queries):
+            bufs = [None if x is None else np.ascontiguousarray(x, np.int8).reshape(21, -1) for x in (paf, p3f, par_, p3r)]
+            ids = np.ascontiguousarray(ids, np.uint32)
+            keep.append((ids, bufs))
+            arr[i].pAA_fwd, arr[i].p3Di_fwd, arr[i].pAA_rev, arr[i].p3Di_rev = [None if b is None else b.ctypes.data for b in bufs]
+            arr[i].L, arr[i].n, arr[i].targetIds = bufs[1].shape[1], len(ids), ids.ctypes.data
+        return keep, arr
+
+    def sw_multi_dir_p(self, queries, direction, selections=None, gap_open=10, gap_extend=1):
+        """Profile queries (fsgpu_sw_multi_dir_p): list of (pAA_fwd|None, p3Di_fwd, pAA_rev|None, p3Di_rev, target_ids), each table int8 [21, L] --
+        profile_decode's output.  One direction for the selected pairs; returns one SWRES array per query (unselected entries stay zero)."""
+        nq = len(queries)
+        keep, arr = self._pqueries(queries)
+        total = sum(len(k[0]) for k in keep)
+        out = np.zeros(max(1, total), SWRES_DT)
+        selp = nselp = None
+        if selections is not None:
+            sels = [np.ascontiguousarray(x, np.int32) for x in selections]
+            keep.append(sels)
+            selp = (C.c_void_p * nq)(*[x.ctypes.data for x in sels])
+            nselp = (C.c_int32 * nq)(*[len(x) for x in sels])
+        self._chk(lib().fsgpu_sw_multi_dir_p(self.h, C.cast(arr, C.c_void_p), nq, gap_open, gap_extend, direction,
+                                             None if selp is None else C.cast(selp, C.c_void_p), None if nselp is None else C.cast(nselp, C.c_void_p),
+                                             out.ctypes.data), "fsgpu_sw_multi_dir_p")
+        res, b = [], 0
+        for k in keep[:nq]:
+            res.append(out[b:b + len(k[0])].copy()); b += len(k[0])
+        return res
+
+    def sw_multi_p(self, queries, gap_open=10, gap_extend=1):
+        """both directions of profile queries in one submission (fsgpu_sw_multi_p); queries as in sw_multi_dir_p.  Returns (fwd arrays, rev arrays)."""
+        keep, arr = self._pqueries(queries)
+        total = sum(len(k[0]) for k in keep)
+        fwd, rev = np.zeros(max(1, total), SWRES_DT), np.zeros(max(1, total), SWRES_DT)
+        self._chk(lib().fsgpu_sw_multi_p(self.h, C.cast(arr, C.c_void_p), len(queries), gap_open, gap_extend, fwd.ctypes.data, rev.ctypes.data), "fsgpu_sw_multi_p")
+        rf, rr, b = [], [], 0
+        for k in keep:
+            rf.append(fwd[b:b + len(k[0])].copy()); rr.append(rev[b:b + len(k[0])].copy()); b += len(k[0])
+        return rf, rr
+
     def sw_scan_c(self, mat3di, matAA, queries, cutoffs, gap_open=10, gap_extend=1, cap=None):
         """Whole-database forward pass with the selection on the device (fsgpu_sw_scan_c).  queries: tuples as for sw_multi_dir_c without the
         target ids (a seventh element is ignored); cutoffs: one score per query.  Returns [(ids, records)] per query: ascending target ids and the
@@ -971,6 +1025,77 @@ class Search:
             raise FsgpuError(f"prefilter_batch rc={rc}: {lib().fshost_search_error(self.h).decode()}")
         return [hits[i * K:i * K + nh[i]].copy() for i in range(nq)]
 
+    # ---- profile queries: entries = (AA entry bytes, 3Di entry bytes) of a profile database, decoded here (profile_decode) ----
+    class _PQ(C.Structure):
+        _fields_ = [("codesAA", C.c_void_p), ("codes3Di", C.c_void_p), ("pAA", C.c_void_p), ("pAArev", C.c_void_p), ("p3Di", C.c_void_p), ("p3Direv", C.c_void_p),
+                    ("L", C.c_int32), ("reserved", C.c_int32)]
+
+    def _pqueries(self, entries):
+        keep, arr = [], (Search._PQ * max(1, len(entries)))()
+        for i, (ea, e3) in enumerate(entries):
+            ca, _, aF, aR = profile_decode(ea)
+            c3, _, sF, sR = profile_decode(e3)
+            if len(ca) != len(c3):
+                raise FsgpuError("AA / 3Di profiles do not match")
+            keep.append((ca, c3, aF, aR, sF, sR))
+            arr[i].codesAA, arr[i].codes3Di, arr[i].pAA, arr[i].pAArev, arr[i].p3Di, arr[i].p3Direv = [x.ctypes.data for x in keep[-1]]
+            arr[i].L, arr[i].reserved = len(c3), 0
+        return keep, arr
+
+    def prefilter_profile(self, entry_3di, identity=-1):
+        """fshost_search_prefilter_profile: the hit list of one profile query (the pssm is its 3Di alignment profile)"""
+        _, _, prof, _ = profile_decode(entry_3di)
+        hits = np.zeros(self.par.maxResListLen, HIT_DT)
+        n = lib().fshost_search_prefilter_profile(self.h, _ptr(prof), prof.shape[1], identity, _ptr(hits))
+        if n < 0:
+            raise FsgpuError(f"prefilter_profile rc={n}: {lib().fshost_search_error(self.h).decode()}")
+        return hits[:n]
+
+    def prefilter_batch_profile(self, entries_3di, identity=None):
+        nq = len(entries_3di)
+        profs = [profile_decode(e)[2] for e in entries_3di]
+        pp = (C.c_void_p * max(nq, 1))(*[x.ctypes.data for x in profs])
+        Ls = np.array([x.shape[1] for x in profs], np.int32)
+        ident = None if identity is None else np.ascontiguousarray(identity, np.int64)
+        K = self.par.maxResListLen
+        hits, nh = np.zeros(max(1, nq * K), HIT_DT), np.zeros(max(nq, 1), np.int32)
+        rc = lib().fshost_search_prefilter_batch_profile(self.h, nq, C.cast(pp, C.c_void_p), _ptr(Ls), _ptr(ident), _ptr(hits), _ptr(nh))
+        if rc != 0:
+            raise FsgpuError(f"prefilter_batch_profile rc={rc}: {lib().fshost_search_error(self.h).decode()}")
+        return [hits[i * K:i * K + nh[i]].copy() for i in range(nq)]
+
+    def _bts(self, res):
+        return [lib().fshost_search_backtrace(self.h, C.c_void_p(res[k:k + 1].ctypes.data)).decode() for k in range(len(res))]
+
+    def align_profile(self, entry_aa, entry_3di, target_ids, identity=-1):
+        """fshost_search_align_profile -> (records, backtraces) of one profile query"""
+        keep, arr = self._pqueries([(entry_aa, entry_3di)])
+        t = np.ascontiguousarray(target_ids, np.uint32)
+        res = np.zeros(max(1, len(t)), RESULT_DT)
+        n = lib().fshost_search_align_profile(self.h, C.cast(arr, C.c_void_p), identity, _ptr(t), len(t), _ptr(res))
+        if n < 0:
+            e = FsgpuError(f"align_profile rc={n}: {lib().fshost_search_error(self.h).decode()}")
+            e.rc = n
+            raise e
+        return res[:n], self._bts(res[:n])
+
+    def align_batch_profile(self, entries, target_id_lists, identity=None):
+        """fshost_search_align_batch_profile; entries: [(AA entry, 3Di entry)] -> ([records], [backtraces]) per query"""
+        nq = len(entries)
+        keep, arr = self._pqueries(entries)
+        ts = [np.ascontiguousarray(x, np.uint32) for x in target_id_lists]
+        res = [np.zeros(max(1, len(t)), RESULT_DT) for t in ts]
+        P = C.c_void_p * max(nq, 1)
+        pt, pr = P(*[x.ctypes.data for x in ts]), P(*[x.ctypes.data for x in res])
+        ns = np.array([len(x) for x in ts], np.int32)
+        ident = None if identity is None else np.ascontiguousarray(identity, np.int64)
+        nres = np.zeros(max(nq, 1), np.int32)
+        rc = lib().fshost_search_align_batch_profile(self.h, nq, C.cast(arr, C.c_void_p), _ptr(ident), C.cast(pt, C.c_void_p), _ptr(ns), C.cast(pr, C.c_void_p), _ptr(nres))
+        if rc != 0:
+            raise FsgpuError(f"align_batch_profile rc={rc}: {lib().fshost_search_error(self.h).decode()}")
+        out = [res[i][:nres[i]] for i in range(nq)]
+        return out, [self._bts(o) for o in out]
+
     def align(self, qAA, q3di, target_ids, identity=-1, with_backtrace=False):
         qa = np.ascontiguousarray(qAA, np.uint8)
         q3 = np.ascontiguousarray(q3di, np.uint8)
@@ -1232,6 +1357,27 @@ def ca_decode(entry, L):
     if lib().fshost_ca_decode(_ptr(buf), len(buf), int(L), _ptr(out)) != 0:
         raise FsgpuError(f"ca_decode: an entry of {len(buf)} bytes is too short for {L} residues")
     return out
+
+
+def profile_decode(entry):
+    """fshost_profile_decode (Sequence::mapProfile): the bytes of a profile entry without its terminator -> (codes uint8 [L], consensus uint8 [L],
+    profile int8 [21, L], reversed profile int8 [21, L]).  A damaged entry raises FsgpuError with the library's reason."""
+    buf = np.frombuffer(bytes(entry), np.uint8)
+    err = C.create_string_buffer(256)
+    L = lib().fshost_profile_decode(_ptr(buf) if len(buf) else None, len(buf), None, None, None, None, err, len(err))
+    if L < 0:
+        raise FsgpuError(err.value.decode())
+    codes, cons = np.zeros(L, np.uint8), np.zeros(L, np.uint8)
+    prof, rev = np.zeros((21, L), np.int8), np.zeros((21, L), np.int8)
+    if L and lib().fshost_profile_decode(_ptr(buf), len(buf), _ptr(codes), _ptr(cons), _ptr(prof), _ptr(rev), err, len(err)) != L:
+        raise FsgpuError(err.value.decode())
+    return codes, cons, prof, rev
+
+
+def profile_bias(profile):
+    """fshost_profile_bias: the bias of ssw_init's profile branch for an int8 [21, L] alignment profile; the gapless scan's cap is 255 - bias"""
+    p = np.ascontiguousarray(profile, np.int8).reshape(21, -1)
+    return lib().fshost_profile_bias(_ptr(p), p.shape[1])
 
 
 def lddt_average(cols):

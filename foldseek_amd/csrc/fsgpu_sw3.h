@@ -15,3 +15,5 @@ int fsgpuLaunchSw3AA(fsgpu_ctx *ctx, int rlo, int HL, const fs::Sw3Args &sa, int
 // images of nq queries; maxDwords = dwords of the largest image (sizes the grid)
 int fsgpuLaunchSw3Image(fsgpu_ctx *ctx, const fs::Sw3ImgQuery *dq, int nq, int maxDwords, const uint8_t *data, const int8_t *mat3, const int8_t *matA,
                         uint32_t *img, bool hasAA, hipStream_t stream);
+// the same for profile queries (k_sw3_image_profile): data holds every query's int8 tables
+int fsgpuLaunchSw3ImageProfile(fsgpu_ctx *ctx, const fs::Sw3ImgQuery *dq, int nq, int maxDwords, const int8_t *data, uint32_t *img, bool hasAA, hipStream_t stream);

@@ -59,4 +59,14 @@ int fsgpuLaunchSw3Image(fsgpu_ctx *ctx, const Sw3ImgQuery *dq, int nq, int maxDw
     }
     return FSGPU_OK;
 }
+
+int fsgpuLaunchSw3ImageProfile(fsgpu_ctx *ctx, const Sw3ImgQuery *dq, int nq, int maxDwords, const int8_t *data, uint32_t *img, bool hasAA, hipStream_t stream) {
+    if (nq <= 0) return FSGPU_OK;
+    const int bx = std::max(1, std::min(64, (maxDwords + 1023) / 1024));
+    for (int i0 = 0; i0 < nq; i0 += 65535) {
+        hipLaunchKernelGGL(k_sw3_image_profile, dim3(bx, std::min(65535, nq - i0)), dim3(256), 0, stream, dq + i0, data, img, hasAA ? 1 : 0);
+        HIPCHK(hipGetLastError());
+    }
+    return FSGPU_OK;
+}
 #endif

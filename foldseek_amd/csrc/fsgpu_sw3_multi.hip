@@ -15,6 +15,8 @@
 // biases; the LDS images are built by k_sw3_image.  Queries of up to 32 * 16 rows run with 32 lanes per target pair (four targets per
 // wave), up to 64 * 16 rows with 64 lanes; longer ones and the int32 re-run of int16-saturated pairs go through the profile-based
 // entry points with profiles materialised here.
+// Profile queries (fsgpu_sw_multi_dir_p / _p: a query IS its int8 tables) run through the same plan: Sw3Plan::pq marks them, and only the three steps
+// that look at where a score comes from -- sw3Validate, Sw3Plan::profilesOf, sw3Images (k_sw3_image_profile) -- branch on it.
 static bool sw3Class(int L, int &R, int &HL) {
     if (L <= 32 * kSw3MaxR) { HL = 32; R = (L + 31) / 32; return true; }
     if (L <= 64 * kSw3MaxR) { HL = 64; R = (L + 63) / 64; return true; }
@@ -34,7 +36,18 @@ static void sw3Materialize(const int8_t *mat, const uint8_t *codes, const int8_t
 
 constexpr int kShapeHL[3] = {16, 32, 64};       // lanes per target pair of the three shapes
 
+// a profile query's int8 table as the int16 word profile (ssw_init's profile_word_linear: the table itself)
+static void sw3Widen(const int8_t *t, int L, std::vector<int16_t> &out) {
+    out.resize((size_t) kAlphabet * L);
+    for (size_t k = 0; k < out.size(); k++) out[k] = (int16_t) t[k];
+}
+
 void Sw3Plan::profilesOf(int i, Sw3Prof &pr) const {
+    if (pq) {
+        sw3Widen(pq[i].p3Di_fwd, pq[i].L, pr.sF); sw3Widen(pq[i].p3Di_rev, pq[i].L, pr.sR);
+        if (hasAA) { sw3Widen(pq[i].pAA_fwd, pq[i].L, pr.aF); sw3Widen(pq[i].pAA_rev, pq[i].L, pr.aR); }
+        return;
+    }
     sw3Materialize(mat3Di, q[i].q3Di, q[i].cb3Di_fwd, q[i].L, false, pr.sF);
     sw3Materialize(mat3Di, q[i].q3Di, q[i].cb3Di_rev, q[i].L, true, pr.sR);
     if (hasAA) { sw3Materialize(matAA, q[i].qAA, q[i].cbAA_fwd, q[i].L, false, pr.aF); sw3Materialize(matAA, q[i].qAA, q[i].cbAA_rev, q[i].L, true, pr.aR); }
@@ -49,8 +62,12 @@ int sw3Validate(fsgpu_ctx *ctx, Sw3Plan &p) {
     const fsgpu_sw_cquery *q = p.q;
     p.base.assign(p.nq + 1, 0);
     for (int i = 0; i < p.nq; i++) {
-        if (!q[i].q3Di || (p.hasAA && !q[i].qAA) || q[i].L <= 0 || q[i].L > FSGPU_MAX_SEQ_LEN || q[i].n < 0 || (q[i].n > 0 && !q[i].targetIds)) { ctx->err = who + ": bad query"; return FSGPU_E_ARG; }
-        for (int k = 0; k < q[i].L; k++) if (q[i].q3Di[k] >= kAlphabet || (p.hasAA && q[i].qAA[k] >= kAlphabet)) { ctx->err = who + ": residue code out of range"; return FSGPU_E_ARG; }
+        // the score source: four tables or the two 3Di ones, the same for every query of the call (any int8 is a score) / codes below 21
+        const bool src = p.pq ? p.pq[i].p3Di_fwd && p.pq[i].p3Di_rev && (p.pq[i].pAA_fwd != nullptr) == p.hasAA && (p.pq[i].pAA_rev != nullptr) == p.hasAA
+                              : q[i].q3Di && (!p.hasAA || q[i].qAA);
+        if (!src || q[i].L <= 0 || q[i].L > FSGPU_MAX_SEQ_LEN || q[i].n < 0 || (q[i].n > 0 && !q[i].targetIds)) { ctx->err = who + ": bad query"; return FSGPU_E_ARG; }
+        if (!p.pq)
+            for (int k = 0; k < q[i].L; k++) if (q[i].q3Di[k] >= kAlphabet || (p.hasAA && q[i].qAA[k] >= kAlphabet)) { ctx->err = who + ": residue code out of range"; return FSGPU_E_ARG; }
         p.base[i + 1] = p.base[i] + (size_t) q[i].n;
         if ((rc = swCheckPairs(ctx, p.who, q[i].targetIds, q[i].n, p.sel != nullptr, p.sel ? p.sel[i] : nullptr, p.nSelAll(i))) != FSGPU_OK) return rc;
     }
@@ -159,12 +176,28 @@ int sw3Images(fsgpu_ctx *ctx, const Sw3Plan &p) {
     const int nq = p.nq;
     const bool hasAA = p.hasAA;
     int rc;
-    uint64_t sig = 0xcbf29ce484222325ull ^ (uint64_t) nq ^ ((uint64_t) hasAA << 40);
-    sig = hashWords(sig, p.mat3Di, kAlphabet * kAlphabet);
-    if (hasAA) sig = hashWords(sig, p.matAA, kAlphabet * kAlphabet);
+    // what an image is made of, all of it: for compact queries the matrices, codes and biases, for profile queries every byte of their tables; the
+    // kind is part of the key, so a profile call never finds the images of a compact call of the same lengths in place, nor the other way round
+    const bool prof = p.pq != nullptr;
+    const std::string who = p.who;
+    uint64_t sig = 0xcbf29ce484222325ull ^ (uint64_t) nq ^ ((uint64_t) hasAA << 40) ^ ((uint64_t) prof << 41);
+    if (!prof) {
+        sig = hashWords(sig, p.mat3Di, kAlphabet * kAlphabet);
+        if (hasAA) sig = hashWords(sig, p.matAA, kAlphabet * kAlphabet);
+    }
+    // bytes a query ships to the builder: [q3Di][qAA][four bias vectors], or its tables in the order k_sw3_image_profile reads them
+    auto tablesOf = [&](int i, const int8_t *(&t)[4]) { t[0] = p.pq[i].p3Di_fwd; t[1] = hasAA ? p.pq[i].pAA_fwd : p.pq[i].p3Di_rev; t[2] = p.pq[i].p3Di_rev; t[3] = p.pq[i].pAA_rev; return hasAA ? 4 : 2; };
+    auto dataBytesOf = [&](int i) { return ((prof ? (size_t) (hasAA ? 4 : 2) * kAlphabet : (size_t) 6) * q[i].L + 15) / 16 * 16; };
     for (int i = 0; i < nq; i++) {
         if (p.cR[i] == 0) continue;
         const size_t L = (size_t) q[i].L;
+        if (prof) {
+            const int8_t *t[4];
+            const int nt = tablesOf(i, t);
+            sig ^= (uint64_t) i * 0x9E3779B97F4A7C15ull ^ L;
+            for (int c = 0; c < nt; c++) sig = hashWords(sig, t[c], (size_t) kAlphabet * L);
+            continue;
+        }
         sig = hashWords(sig ^ (uint64_t) i * 0x9E3779B97F4A7C15ull ^ L, q[i].q3Di, L);
         if (hasAA) sig = hashWords(sig, q[i].qAA, L);
         const int8_t *cbs[4] = {q[i].cb3Di_fwd, q[i].cbAA_fwd, q[i].cb3Di_rev, q[i].cbAA_rev};
@@ -185,19 +218,19 @@ int sw3Images(fsgpu_ctx *ctx, const Sw3Plan &p) {
             if (p.nShape(i, shape) == 0) continue;
             const int HL = kShapeHL[shape], R = (q[i].L + HL - 1) / HL;
             const size_t one = (size_t) 2 * sw3ImageBytes(R, HL, hasAA) / 4;
-            if (imgDw + one >= (1ull << 32)) { ctx->err = "fsgpu_sw_multi_dir_c: images of one call exceed 16 GiB"; return FSGPU_E_NOMEM; }
+            if (imgDw + one >= (1ull << 32)) { ctx->err = who + ": images of one call exceed 16 GiB"; return FSGPU_E_NOMEM; }
             ctx->s3ImgOff[3 * i + shape] = (uint32_t) imgDw; imgDw += one; maxDw = std::max(maxDw, (int) one);
             nImg++;
         }
-        dataBytes += ((size_t) 6 * q[i].L + 15) / 16 * 16;
+        dataBytes += dataBytesOf(i);
     }
     const size_t descBytes = ((size_t) nImg * sizeof(Sw3ImgQuery) + 15) / 16 * 16, matOff = descBytes, dataOff0 = matOff + 1024;
     if ((rc = ensurePinned(ctx, ctx->hS3build, dataOff0 + dataBytes)) != FSGPU_OK) return rc;
     if ((rc = ensureAll(ctx, {{ctx->s3build, dataOff0 + dataBytes}, {ctx->s3img, imgDw * 4}})) != FSGPU_OK) return rc;
     unsigned char *hb = (unsigned char *) ctx->hS3build.p;
     Sw3ImgQuery *hd = (Sw3ImgQuery *) hb;
-    memcpy(hb + matOff, p.mat3Di, kAlphabet * kAlphabet);
-    if (hasAA) memcpy(hb + matOff + 512, p.matAA, kAlphabet * kAlphabet);
+    if (!prof) memcpy(hb + matOff, p.mat3Di, kAlphabet * kAlphabet);
+    if (!prof && hasAA) memcpy(hb + matOff + 512, p.matAA, kAlphabet * kAlphabet);
     size_t dpos = dataOff0;
     int k = 0;
     for (int i = 0; i < nq; i++) {
@@ -211,17 +244,24 @@ int sw3Images(fsgpu_ctx *ctx, const Sw3Plan &p) {
             k++;
         }
         unsigned char *d = hb + dpos;
-        memcpy(d, q[i].q3Di, L);
-        if (hasAA) memcpy(d + L, q[i].qAA, L); else memset(d + L, 0, L);
-        const int8_t *cbs[4] = {q[i].cb3Di_fwd, q[i].cbAA_fwd, q[i].cb3Di_rev, q[i].cbAA_rev};
-        for (int c = 0; c < 4; c++) { if (cbs[c]) memcpy(d + (2 + c) * L, cbs[c], L); else memset(d + (2 + c) * L, 0, L); }
-        dpos += (6 * L + 15) / 16 * 16;
-        if (dpos - dataOff0 >= (1ull << 32)) { ctx->err = "fsgpu_sw_multi_dir_c: query data of one call exceeds 4 GiB"; return FSGPU_E_NOMEM; }
+        if (prof) {
+            const int8_t *t[4];
+            const int nt = tablesOf(i, t);
+            for (int c = 0; c < nt; c++) memcpy(d + (size_t) c * kAlphabet * L, t[c], (size_t) kAlphabet * L);
+        } else {
+            memcpy(d, q[i].q3Di, L);
+            if (hasAA) memcpy(d + L, q[i].qAA, L); else memset(d + L, 0, L);
+            const int8_t *cbs[4] = {q[i].cb3Di_fwd, q[i].cbAA_fwd, q[i].cb3Di_rev, q[i].cbAA_rev};
+            for (int c = 0; c < 4; c++) { if (cbs[c]) memcpy(d + (2 + c) * L, cbs[c], L); else memset(d + (2 + c) * L, 0, L); }
+        }
+        dpos += dataBytesOf(i);
+        if (dpos - dataOff0 >= (1ull << 32)) { ctx->err = who + ": query data of one call exceeds 4 GiB"; return FSGPU_E_NOMEM; }
     }
     HIPCHK(hipMemcpyAsync(ctx->s3build.p, hb, dpos, hipMemcpyHostToDevice, p.S));
     const unsigned char *db = (const unsigned char *) ctx->s3build.p;
-    rc = fsgpuLaunchSw3Image(ctx, (const Sw3ImgQuery *) db, nImg, maxDw, db + dataOff0, (const int8_t *) (db + matOff), (const int8_t *) (db + matOff + 512),
-                             (uint32_t *) ctx->s3img.p, hasAA, p.S);
+    rc = prof ? fsgpuLaunchSw3ImageProfile(ctx, (const Sw3ImgQuery *) db, nImg, maxDw, (const int8_t *) (db + dataOff0), (uint32_t *) ctx->s3img.p, hasAA, p.S)
+              : fsgpuLaunchSw3Image(ctx, (const Sw3ImgQuery *) db, nImg, maxDw, db + dataOff0, (const int8_t *) (db + matOff), (const int8_t *) (db + matOff + 512),
+                                    (uint32_t *) ctx->s3img.p, hasAA, p.S);
     if (rc != FSGPU_OK) return rc;
     ctx->s3Sig = sig;
     ctx->s3Plan[8] += (uint32_t) nImg;
@@ -422,13 +462,9 @@ static int sw3RerunSaturated(fsgpu_ctx *ctx, const Sw3Plan &p) {
     return FSGPU_OK;
 }
 
-static int sw3MultiImpl(fsgpu_ctx *ctx, const int8_t *mat3Di, const int8_t *matAA, const fsgpu_sw_cquery *q, int nq, int gapOpen, int gapExtend, int dir,
-                        const int32_t *const *sel, const int32_t *nsel, fsgpu_swres *out, fsgpu_swres *out2) {
-    if (!ctx || !mat3Di || nq < 0 || (nq > 0 && (!q || !out)) || dir < 0 || dir > 2 || (dir == 2 && nq > 0 && !out2) || ((sel == nullptr) != (nsel == nullptr))) return FSGPU_E_ARG;
-    Sw3Plan p;
-    p.mat3Di = mat3Di; p.matAA = matAA; p.q = q; p.nq = nq; p.gapOpen = gapOpen; p.gapExtend = gapExtend; p.dir = dir;
-    p.sel = sel; p.nsel = nsel; p.out = out; p.out2 = out2;
-    p.hasAA = matAA != nullptr;
+// one submission of a filled-in plan (who, the score source, q, nq, gap costs, dir, sel / nsel, out / out2, hasAA)
+static int sw3Run(fsgpu_ctx *ctx, Sw3Plan &p) {
+    const int dir = p.dir;
     p.slot = dir == 1 ? 1 : 0; p.nDirs = dir == 2 ? 2 : 1; p.dir0 = dir == 2 ? 0 : dir;
     p.S = ctx->swHi ? ctx->swHi : ctx->stream;
     int rc;
@@ -460,7 +496,41 @@ static int sw3MultiImpl(fsgpu_ctx *ctx, const int8_t *mat3Di, const int8_t *matA
     return FSGPU_OK;
 }
 
+static int sw3MultiImpl(fsgpu_ctx *ctx, const int8_t *mat3Di, const int8_t *matAA, const fsgpu_sw_cquery *q, int nq, int gapOpen, int gapExtend, int dir,
+                        const int32_t *const *sel, const int32_t *nsel, fsgpu_swres *out, fsgpu_swres *out2) {
+    if (!ctx || !mat3Di || nq < 0 || (nq > 0 && (!q || !out)) || dir < 0 || dir > 2 || (dir == 2 && nq > 0 && !out2) || ((sel == nullptr) != (nsel == nullptr))) return FSGPU_E_ARG;
+    Sw3Plan p;
+    p.mat3Di = mat3Di; p.matAA = matAA; p.q = q; p.nq = nq; p.gapOpen = gapOpen; p.gapExtend = gapExtend; p.dir = dir;
+    p.sel = sel; p.nsel = nsel; p.out = out; p.out2 = out2;
+    p.hasAA = matAA != nullptr;
+    return sw3Run(ctx, p);
+}
+
+// profile queries: the plan's q[] carries their L, n and targetIds, the tables stay where the caller has them
+static int sw3MultiImplP(fsgpu_ctx *ctx, const char *who, const fsgpu_sw_pquery *pq, int nq, int gapOpen, int gapExtend, int dir,
+                         const int32_t *const *sel, const int32_t *nsel, fsgpu_swres *out, fsgpu_swres *out2) {
+    if (!ctx || nq < 0 || (nq > 0 && (!pq || !out)) || dir < 0 || dir > 2 || (dir == 2 && nq > 0 && !out2) || ((sel == nullptr) != (nsel == nullptr))) return FSGPU_E_ARG;
+    std::vector<fsgpu_sw_cquery> shadow((size_t) nq);
+    for (int i = 0; i < nq; i++) { shadow[i] = fsgpu_sw_cquery{}; shadow[i].L = pq[i].L; shadow[i].n = pq[i].n; shadow[i].targetIds = pq[i].targetIds; }
+    Sw3Plan p;
+    p.who = who;
+    p.mat3Di = p.matAA = nullptr; p.pq = pq; p.q = shadow.data(); p.nq = nq; p.gapOpen = gapOpen; p.gapExtend = gapExtend; p.dir = dir;
+    p.sel = sel; p.nsel = nsel; p.out = out; p.out2 = out2;
+    p.hasAA = nq > 0 && pq[0].pAA_fwd != nullptr;
+    return sw3Run(ctx, p);
+}
+
 extern "C" {
+
+int fsgpu_sw_multi_dir_p(fsgpu_ctx *ctx, const fsgpu_sw_pquery *q, int nq, int gapOpen, int gapExtend, int dir,
+                         const int32_t *const *sel, const int32_t *nsel, fsgpu_swres *out) {
+    if (dir != 0 && dir != 1) return FSGPU_E_ARG;
+    return sw3MultiImplP(ctx, "fsgpu_sw_multi_dir_p", q, nq, gapOpen, gapExtend, dir, sel, nsel, out, nullptr);
+}
+
+int fsgpu_sw_multi_p(fsgpu_ctx *ctx, const fsgpu_sw_pquery *q, int nq, int gapOpen, int gapExtend, fsgpu_swres *fwd, fsgpu_swres *rev) {
+    return sw3MultiImplP(ctx, "fsgpu_sw_multi_p", q, nq, gapOpen, gapExtend, 2, nullptr, nullptr, fwd, rev);
+}
 
 int fsgpu_sw_multi_dir_c(fsgpu_ctx *ctx, const int8_t *mat3Di, const int8_t *matAA, const fsgpu_sw_cquery *q, int nq, int gapOpen, int gapExtend, int dir,
                          const int32_t *const *sel, const int32_t *nsel, fsgpu_swres *out) {

@@ -15,6 +15,9 @@ struct Sw3Plan {
     const char *who = "fsgpu_sw_multi_dir_c";         // the entry, for its messages
     const int8_t *mat3Di, *matAA;
     const fsgpu_sw_cquery *q;
+    // profile queries (fsgpu_sw_multi_dir_p / _p): the int8 tables of query i are pq[i]'s; q[i] then carries L, n and targetIds alone (no codes, no
+    // biases) and mat3Di / matAA are not read.  What differs is where a score comes from: sw3Validate, profilesOf and sw3Images branch on it.
+    const fsgpu_sw_pquery *pq = nullptr;
     int nq, gapOpen, gapExtend, dir;                  // dir 0 / 1: one direction into out; dir 2: both directions in ONE submission (forward into out, reversed into out2)
     const int32_t *const *sel = nullptr;
     const int32_t *nsel = nullptr;

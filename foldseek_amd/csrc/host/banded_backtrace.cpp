@@ -17,10 +17,11 @@
 
 namespace fsh {
 
-// banded_sw (:1723-1957) for substitution-matrix queries.  q* / cb* start at qStart, t* at dbStart.  Returns false when the
-// trace-back meets an impossible direction code (the reference prints "Trace back error" and returns no cigar).
-bool bandedBacktrace(const Matrix &mAA, const Matrix &m3Di, const uint8_t *qAA, const uint8_t *q3Di, const int8_t *cbAA, const int8_t *cbSS,
-                     int qLen, const uint8_t *tAA, const uint8_t *t3Di, int dbLen, int score, int gapOpen, int gapExtend, std::string &path) {
+// banded_sw (:1723-1957); match(i, j) is the substitution score of query row i (from qStart) and target column j (from dbStart): the one thing the
+// reference's SUBSTITUTIONMATRIX and PROFILE forms differ in (:1832-1839).  Returns false when the trace-back meets an impossible direction code
+// (the reference prints "Trace back error" and returns no cigar).
+template <class Match>
+static bool bandedCore(int qLen, int dbLen, int score, int gapOpen, int gapExtend, std::string &path, Match match) {
     path.clear();
     if (qLen <= 0 || dbLen <= 0) return false;
     int band = std::abs(dbLen - qLen) + 1;
@@ -31,7 +32,6 @@ bool bandedBacktrace(const Matrix &mAA, const Matrix &m3Di, const uint8_t *qAA, 
     // column of the scoring matrix -> slot in one band line; (state p, column) -> slot in one direction line
     auto slotU = [](int w, int i, int j) { int x = i - w; x = x > 0 ? x : 0; return j - x + 1; };
     auto slotD = [](int w, int i, int j, int p) { int x = i - w; x = x > 0 ? x : 0; return (j - x) * 3 + p; };
-    const int nA = mAA.n, n3 = m3Di.n;
     do {
         width = (int64_t) band * 2 + 3; widthD = (int64_t) band * 2 + 1;
         hPrev.assign((size_t) width + 2, 0); ePrev.assign((size_t) width + 2, 0); hCur.assign((size_t) width + 2, 0);
@@ -43,7 +43,6 @@ bool bandedBacktrace(const Matrix &mAA, const Matrix &m3Di, const uint8_t *qAA, 
             int f = 0, u = 0;
             hPrev[0] = ePrev[0] = hPrev[edge] = ePrev[edge] = hCur[0] = 0;
             int8_t *line = dir.data() + widthD * i * 3;
-            const int rowScoreBias = (int) cbAA[i] + (int) cbSS[i];
             for (int j = beg; j <= end; j++) {
                 u = slotU(band, i, j);
                 const int e = slotU(band, i - 1, j), b = slotU(band, i, j - 1), d = slotU(band, i - 1, j - 1);
@@ -58,7 +57,7 @@ bool bandedBacktrace(const Matrix &mAA, const Matrix &m3Di, const uint8_t *qAA, 
                 line[df] = t1 > t2 ? 5 : 4;
                 const int e1 = ePrev[u] > 0 ? ePrev[u] : 0, f1 = f > 0 ? f : 0;
                 t1 = e1 > f1 ? e1 : f1;
-                t2 = hPrev[d] + (int) mAA.tiny[(size_t) qAA[i] * nA + tAA[j]] + (int) m3Di.tiny[(size_t) q3Di[i] * n3 + t3Di[j]] + rowScoreBias;
+                t2 = hPrev[d] + match(i, j);
                 hCur[u] = t1 > t2 ? t1 : t2;
                 if (hCur[u] > best) best = hCur[u];
                 line[dh] = t1 <= t2 ? (int8_t) 1 : (e1 > f1 ? line[de] : line[df]);
@@ -91,6 +90,23 @@ bool bandedBacktrace(const Matrix &mAA, const Matrix &m3Di, const uint8_t *qAA, 
     rev.push_back('M');
     path.assign(rev.rbegin(), rev.rend());
     return true;
+}
+
+// substitution-matrix queries.  q* / cb* start at qStart, t* at dbStart.
+bool bandedBacktrace(const Matrix &mAA, const Matrix &m3Di, const uint8_t *qAA, const uint8_t *q3Di, const int8_t *cbAA, const int8_t *cbSS,
+                     int qLen, const uint8_t *tAA, const uint8_t *t3Di, int dbLen, int score, int gapOpen, int gapExtend, std::string &path) {
+    const int nA = mAA.n, n3 = m3Di.n;
+    return bandedCore(qLen, dbLen, score, gapOpen, gapExtend, path, [&](int i, int j) {
+        return (int) mAA.tiny[(size_t) qAA[i] * nA + tAA[j]] + (int) m3Di.tiny[(size_t) q3Di[i] * n3 + t3Di[j]] + (int) cbAA[i] + (int) cbSS[i];
+    });
+}
+
+// profile queries: pAA / p3Di are the WHOLE alignment profiles [21 * L], the rectangle starts at query row qStart; t* start at dbStart
+bool bandedBacktraceProfile(const int8_t *pAA, const int8_t *p3Di, int L, int qStart, int qLen, const uint8_t *tAA, const uint8_t *t3Di, int dbLen,
+                            int score, int gapOpen, int gapExtend, std::string &path) {
+    return bandedCore(qLen, dbLen, score, gapOpen, gapExtend, path, [&](int i, int j) {
+        return (int) pAA[(size_t) tAA[j] * L + qStart + i] + (int) p3Di[(size_t) t3Di[j] * L + qStart + i];
+    });
 }
 
 } // namespace fsh

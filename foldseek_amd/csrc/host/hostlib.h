@@ -47,6 +47,8 @@ void blockBacktrace(const Matrix &mAA, const Matrix &m3Di, const uint8_t *qAA, c
 
 // banded_sw with band doubling + trace-back (StructureSmithWaterman.cpp:1723-1957) over the rectangle that starts at the
 // given pointers; path = M / I / D string from the start cell to the end cell.  false: impossible direction code.
+bool bandedBacktraceProfile(const int8_t *pAA, const int8_t *p3Di, int L, int qStart, int qLen, const uint8_t *tAA, const uint8_t *t3Di, int dbLen,
+                            int score, int gapOpen, int gapExtend, std::string &path);
 bool bandedBacktrace(const Matrix &mAA, const Matrix &m3Di, const uint8_t *qAA, const uint8_t *q3Di, const int8_t *cbAA, const int8_t *cbSS,
                      int qLen, const uint8_t *tAA, const uint8_t *t3Di, int dbLen, int score, int gapOpen, int gapExtend, std::string &path);
 

@@ -12,7 +12,7 @@
 
 namespace fsh {
 
-enum { DBTYPE_AMINO_ACIDS = 0, DBTYPE_ALIGNMENT_RES = 5, DBTYPE_PREFILTER_RES = 7 };
+enum { DBTYPE_AMINO_ACIDS = 0, DBTYPE_HMM_PROFILE = 2, DBTYPE_ALIGNMENT_RES = 5, DBTYPE_PREFILTER_RES = 7 };
 enum { DBTYPE_EXTENDED_COMPRESSED = 1, DBTYPE_EXTENDED_GPU = 8 };
 
 class DbReader {

@@ -422,6 +422,41 @@ bool checkMaxSeqLen(const Options &o, const DbReader &r, const std::string &what
     return true;
 }
 
+// ---- profile queries (a query database of type DBTYPE_HMM_PROFILE: result2profile's output, the query of every search round after the first) ----
+bool isProfileDb(const DbReader &r) { return r.dbtype() == DBTYPE_HMM_PROFILE; }
+// positions of entry i: DBReader::getSeqLen of a profile database, (index length - 1) / record size
+uint32_t profileLen(const DbReader &r, size_t i) { return (std::max<uint32_t>(r.entryLen(i), 1u) - 1u) / FSHOST_PROFILE_RECORD; }
+// checkMaxSeqLen for a profile database (its entries are records, not residues)
+bool checkMaxProfileLen(const Options &o, const DbReader &r, std::string &err) {
+    const long maxLen = std::min<long>(o.geti("--max-seq-len", FSGPU_MAX_SEQ_LEN), FSGPU_MAX_SEQ_LEN);
+    for (size_t i = 0; i < r.size(); i++)
+        if ((long) profileLen(r, i) > maxLen) {
+            err = "query profile " + std::to_string(r.key(i)) + " has " + std::to_string(profileLen(r, i)) + " positions: longer than --max-seq-len " + std::to_string(maxLen) +
+                  " (truncation is not implemented on the device path)";
+            return false;
+        }
+    return true;
+}
+// one decoded entry: query letters, alignment profile and reversed profile (fshost_profile_decode)
+struct DecodedProfile {
+    std::vector<uint8_t> codes;
+    std::vector<int8_t> fwd, rev;
+    int L = 0;
+    bool decode(const DbReader &r, size_t i, std::string &err) {
+        const size_t bytes = r.entryLen(i) > 0 ? r.entryLen(i) - 1 : 0;
+        char why[200];
+        const int n = fshost_profile_decode(r.data(i), bytes, nullptr, nullptr, nullptr, nullptr, why, sizeof(why));
+        if (n < 0) { err = "query profile " + std::to_string(r.key(i)) + ": " + why; return false; }
+        L = n;
+        codes.resize((size_t) L + 1); fwd.resize((size_t) 21 * L + 1); rev.resize((size_t) 21 * L + 1);
+        return fshost_profile_decode(r.data(i), bytes, codes.data(), nullptr, fwd.data(), rev.data(), why, sizeof(why)) == n;
+    }
+};
+// the refusal of a module that does not take profile queries
+std::string profileRefusal(const std::string &module, const std::string &why) {
+    return module + ": the query database is a profile database (DBTYPE_HMM_PROFILE), " + why;
+}
+
 // --sort-by-structure-bits 1 (default of the workflow) rescales scores by TM-score x LDDT and needs both C-alpha DBs
 // (structurealign.cpp:182-197): without them the reference warns and turns it off -- so do we; with them it is on (CaBinding).
 bool resolveStructureBits(const Options &o, const std::string &qdb, const std::string &tdb) {
@@ -814,6 +849,9 @@ int fsmod_ungappedprefilter(int argc, const char **argv) {
     par.prefCompBiasScale = (float) o.getd("--comp-bias-corr-scale", 0.15);
     Matrix m3;
     m3.builtin(FSHOST_MAT_3DI, 2.0f, 0.0f);
+    const bool profileQuery = isProfileDb(q);
+    if (profileQuery && o.geti("--gpu-server", 0) != 0) return fail(profileRefusal("ungappedprefilter", "which a gpuserver client cannot send: run without --gpu-server"));
+    if (profileQuery && !checkMaxProfileLen(o, q, err)) return fail(err);
     if (o.geti("--gpu-server", 0) != 0) return ungappedPrefilterViaServer(o, q, t, sameDB, par, m3);
     PaddedTarget pt;
     if (!loadPadded(t, nullptr, m3, nullptr, pt, err)) return fail(err);
@@ -838,6 +876,8 @@ int fsmod_ungappedprefilter(int argc, const char **argv) {
         const size_t batch = 32;
         std::vector<fsgpu_hit> hits(batch * (size_t) par.maxResListLen);
         std::vector<std::vector<uint8_t>> codes(batch);
+        std::vector<DecodedProfile> prof(profileQuery ? batch : 0);
+        std::vector<const int8_t *> pp(batch);
         std::vector<const uint8_t *> pq(batch);
         std::vector<int> Ls(batch), nh(batch);
         std::vector<int64_t> ident(batch);
@@ -849,6 +889,15 @@ int fsmod_ungappedprefilter(int argc, const char **argv) {
             size_t m = 0;
             for (size_t oi = b0; oi < std::min(q.size(), b0 + batch); oi++) {
                 const size_t id = order[oi];
+                if (profileQuery) {
+                    std::string perr;
+                    if (!prof[m].decode(q, id, perr)) { if (!bad++) firstErr = perr; break; }
+                    if (prof[m].L == 0) continue;
+                    pp[m] = prof[m].fwd.data(); Ls[m] = prof[m].L; qid[m] = id;
+                    ident[m] = sameDB ? t.idOf(q.key(id)) : -1;
+                    m++;
+                    continue;
+                }
                 const uint32_t L = q.seqLen(id);
                 if (L == 0) continue;
                 codes[m].resize(L);
@@ -858,8 +907,10 @@ int fsmod_ungappedprefilter(int argc, const char **argv) {
                 ident[m] = sameDB ? t.idOf(q.key(id)) : -1;
                 m++;
             }
+            if (bad) break;
             if (m == 0) continue;
-            if (fshost_search_prefilter_batch(s, (int) m, pq.data(), Ls.data(), ident.data(), hits.data(), nh.data()) != FSGPU_OK) {
+            if ((profileQuery ? fshost_search_prefilter_batch_profile(s, (int) m, pp.data(), Ls.data(), ident.data(), hits.data(), nh.data())
+                              : fshost_search_prefilter_batch(s, (int) m, pq.data(), Ls.data(), ident.data(), hits.data(), nh.data())) != FSGPU_OK) {
                 if (!bad++) firstErr = fshost_search_error(s);
                 break;
             }
@@ -905,6 +956,7 @@ int fsmod_prefilter(int argc, const char **argv) {
     std::string err;
     DbReader q, t;
     if (!q.open(o.pos[0], err) || !t.open(o.pos[1], err)) return fail(err);
+    if (isProfileDb(q)) return fail(profileRefusal("prefilter", "and the k-mer generator for profiles is not implemented on the device path: use ungappedprefilter"));
     const bool sameDB = o.pos[0] == o.pos[1];
     const bool includeIdentical = o.geti("--add-self-matches", 0) != 0;
     if (!checkMaxSeqLen(o, q, "query", err) || !checkMaxSeqLen(o, t, "target", err)) return fail(err);
@@ -1033,13 +1085,18 @@ int fsmod_search(int argc, const char **argv) {
         if (o.pos.size() == 4) return fail("search: <outPrefDB> is not written in the exhaustive mode (--prefilter-mode 2 / --exhaustive-search 1): no prefilter runs");
         if (o.kv.count("--max-rejected")) return fail("search: --max-rejected is not supported in the exhaustive mode (--prefilter-mode 2 / --exhaustive-search 1)");
     }
+    const bool profileQuery = isProfileDb(qA) && isProfileDb(q3);
+    if (isProfileDb(qA) != isProfileDb(q3)) return fail("search: only one of " + o.pos[0] + " and its _ss database is a profile database (DBTYPE_HMM_PROFILE): both must be");
+    if (profileQuery && prefMode == 0) return fail(profileRefusal("search", "and the k-mer generator for profiles is not implemented on the device path: use --prefilter-mode 1"));
+    if (profileQuery && prefMode == 2) return fail(profileRefusal("search", "for which the exhaustive mode (--prefilter-mode 2 / --exhaustive-search 1) is not implemented on the device path: use --prefilter-mode 1"));
+    if (profileQuery && o.geti("--alt-ali", 0) > 0) return fail(profileRefusal("search", "for which --alt-ali is not implemented on the device path (supported: 0)"));
     fshost_params par;
     fillParams(o, par);
     par.prefCompBiasScale = (float) o.getd("--comp-bias-corr-scale", 0.15);    // StructureSearch.cpp:101
     par.alnCompBiasScale = 0.5f;                                               // StructureSearch.cpp:107
     const int kmerThr = o.geti("--k-score", INT_MAX) != INT_MAX ? o.geti("--k-score", 0) : fshost_kmer_threshold((float) o.getd("-s", 9.5), 6);
     const bool structBits = resolveStructureBits(o, o.pos[0], o.pos[1]);
-    if (!checkMaxSeqLen(o, q3, "query", err) || !checkMaxSeqLen(o, t3, "target", err)) return fail(err);
+    if (!(profileQuery ? checkMaxProfileLen(o, q3, err) : checkMaxSeqLen(o, q3, "query", err)) || !checkMaxSeqLen(o, t3, "target", err)) return fail(err);
     const int spaced = o.geti("--spaced-kmer-mode", 1);
     if (prefMode == 0 && (o.geti("-k", 0) != 0 && o.geti("-k", 6) != 6)) return fail("search: only -k 6 is implemented on the device path");
     Matrix m3, mA;
@@ -1093,6 +1150,8 @@ int fsmod_search(int argc, const char **argv) {
         std::vector<std::vector<uint8_t>> cA(batch), c3(batch);
         std::vector<std::vector<int16_t>> thr(batch);
         std::vector<std::vector<int8_t>> prof(batch);
+        std::vector<DecodedProfile> dpA(profileQuery ? batch : 0), dp3(profileQuery ? batch : 0);
+        std::vector<fshost_profile_query> pqs(profileQuery ? batch : 0);
         std::vector<fsgpu_kmer_query> kq(batch);
         std::vector<fsgpu_kmer_hit> khits(prefMode == 0 ? batch * (size_t) maxRes : 1);
         std::vector<uint32_t> kkept(prefMode == 0 ? batch * (size_t) maxRes : 1);
@@ -1124,12 +1183,22 @@ int fsmod_search(int argc, const char **argv) {
             for (size_t k = 0; k < nb; k++) {
                 const size_t id = order[b0 + k];
                 qid[k] = id;
-                const uint32_t L = q3.seqLen(id);
                 const int64_t aid = qA.idOf(q3.key(id));
-                if (aid < 0 || qA.seqLen((size_t) aid) != L) { if (!bad++) firstErr = "query AA / 3Di entries do not match"; break; }
-                cA[k].resize(L + 1); c3[k].resize(L + 1);
-                const char *sA = qA.data((size_t) aid), *s3 = q3.data(id);
-                for (uint32_t i = 0; i < L; i++) { cA[k][i] = mA.aa2num[(unsigned char) sA[i]]; c3[k][i] = m3.aa2num[(unsigned char) s3[i]]; }
+                uint32_t L = 0;
+                if (profileQuery) {
+                    std::string perr;
+                    if (aid < 0) { if (!bad++) firstErr = "query AA / 3Di profiles do not match"; break; }
+                    if (!dp3[k].decode(q3, id, perr) || !dpA[k].decode(qA, (size_t) aid, perr)) { if (!bad++) firstErr = perr; break; }
+                    if (dpA[k].L != dp3[k].L) { if (!bad++) firstErr = "query AA / 3Di profiles do not match"; break; }
+                    L = (uint32_t) dp3[k].L;
+                    pqs[k] = fshost_profile_query{dpA[k].codes.data(), dp3[k].codes.data(), dpA[k].fwd.data(), dpA[k].rev.data(), dp3[k].fwd.data(), dp3[k].rev.data(), (int32_t) L, 0};
+                } else {
+                    L = q3.seqLen(id);
+                    if (aid < 0 || qA.seqLen((size_t) aid) != L) { if (!bad++) firstErr = "query AA / 3Di entries do not match"; break; }
+                    cA[k].resize(L + 1); c3[k].resize(L + 1);
+                    const char *sA = qA.data((size_t) aid), *s3 = q3.data(id);
+                    for (uint32_t i = 0; i < L; i++) { cA[k][i] = mA.aa2num[(unsigned char) sA[i]]; c3[k][i] = m3.aa2num[(unsigned char) s3[i]]; }
+                }
                 ident[k] = (sameDB || includeIdentical) ? t3.idOf(q3.key(id)) : -1;
                 if (ca.on && !ca.queryEntry(q3.key(id), caE[k], caL[k])) { if (!bad++) firstErr = "query key " + std::to_string(q3.key(id)) + " has no C-alpha entry"; break; }
                 Ls[k] = (int) L; pA[k] = cA[k].data(); p3[k] = c3[k].data();
@@ -1219,11 +1288,12 @@ int fsmod_search(int argc, const char **argv) {
                 usFormat += (int64_t) ((nowSec() - t0) * 1e6);
                 continue;
             } else {
-                std::vector<const uint8_t *> gq; std::vector<int> gL, gn; std::vector<int64_t> gi; std::vector<size_t> gk;
-                for (size_t k = 0; k < nb; k++) if (Ls[k] > 0) { gq.push_back(c3[k].data()); gL.push_back(Ls[k]); gi.push_back(ident[k]); gk.push_back(k); }
+                std::vector<const uint8_t *> gq; std::vector<const int8_t *> gp; std::vector<int> gL, gn; std::vector<int64_t> gi; std::vector<size_t> gk;
+                for (size_t k = 0; k < nb; k++) if (Ls[k] > 0) { gq.push_back(c3[k].data()); gp.push_back(profileQuery ? dp3[k].fwd.data() : nullptr); gL.push_back(Ls[k]); gi.push_back(ident[k]); gk.push_back(k); }
                 gn.resize(gq.size());
                 ghits.resize(std::max<size_t>(1, gq.size()) * (size_t) par.maxResListLen);
-                if (!gq.empty() && fshost_search_prefilter_batch(s, (int) gq.size(), gq.data(), gL.data(), gi.data(), ghits.data(), gn.data()) != FSGPU_OK) {
+                if (!gq.empty() && (profileQuery ? fshost_search_prefilter_batch_profile(s, (int) gq.size(), gp.data(), gL.data(), gi.data(), ghits.data(), gn.data())
+                                                 : fshost_search_prefilter_batch(s, (int) gq.size(), gq.data(), gL.data(), gi.data(), ghits.data(), gn.data())) != FSGPU_OK) {
                     if (!bad++) firstErr = fshost_search_error(s);
                     break;
                 }
@@ -1244,7 +1314,9 @@ int fsmod_search(int argc, const char **argv) {
             if (live.empty()) continue;
             std::vector<const uint8_t *> lA, l3; std::vector<const uint32_t *> lT; std::vector<fshost_result *> lR;
             std::vector<int> lL, lN, lres(live.size()); std::vector<int64_t> lI;
+            std::vector<fshost_profile_query> lP;
             for (size_t k : live) {
+                if (profileQuery) lP.push_back(pqs[k]);
                 res[k].resize(ids[k].size() * (size_t) (1 + par.altAlignment) + 1);
                 lA.push_back(pA[k]); l3.push_back(p3[k]); lT.push_back(ids[k].data()); lR.push_back(res[k].data());
                 lL.push_back(Ls[k]); lN.push_back((int) ids[k].size());
@@ -1256,7 +1328,8 @@ int fsmod_search(int argc, const char **argv) {
                 for (size_t k : live) { e.push_back(caE[k]); l.push_back(caL[k]); }
                 fshost_search_set_query_ca(s, (int) live.size(), e.data(), l.data());
             }
-            if (fshost_search_align_batch(s, (int) live.size(), lA.data(), l3.data(), lL.data(), lI.data(), lT.data(), lN.data(), lR.data(), lres.data()) != FSGPU_OK) {
+            if ((profileQuery ? fshost_search_align_batch_profile(s, (int) live.size(), lP.data(), lI.data(), lT.data(), lN.data(), lR.data(), lres.data())
+                              : fshost_search_align_batch(s, (int) live.size(), lA.data(), l3.data(), lL.data(), lI.data(), lT.data(), lN.data(), lR.data(), lres.data())) != FSGPU_OK) {
                 if (!bad++) firstErr = fshost_search_error(s);
                 break;
             }
@@ -1317,7 +1390,11 @@ int fsmod_structurealign(int argc, const char **argv) {
     fillParams(o, par);
     par.alnCompBiasScale = (float) o.getd("--comp-bias-corr-scale", 0.5);
     const bool structBits = resolveStructureBits(o, o.pos[0], o.pos[1]);
-    if (!checkMaxSeqLen(o, q3, "query", err) || !checkMaxSeqLen(o, t3, "target", err)) return fail(err);
+    // a profile search needs BOTH query databases to be profiles (StructureSmithWaterman.cpp:1586-1587); one alone would be read as residues
+    const bool profileQuery = isProfileDb(qA) && isProfileDb(q3);
+    if (isProfileDb(qA) != isProfileDb(q3)) return fail("structurealign: only one of " + o.pos[0] + " and its _ss database is a profile database (DBTYPE_HMM_PROFILE): both must be");
+    if (profileQuery && par.altAlignment > 0) return fail(profileRefusal("structurealign", "for which --alt-ali is not implemented on the device path (supported: 0)"));
+    if (!(profileQuery ? checkMaxProfileLen(o, q3, err) : checkMaxSeqLen(o, q3, "query", err)) || !checkMaxSeqLen(o, t3, "target", err)) return fail(err);
     Matrix m3, mA;
     m3.builtin(FSHOST_MAT_3DI, 2.1f, 0.0f);
     mA.builtin(FSHOST_MAT_BLOSUM62, par.alignmentType == 2 ? 1.4f : 0.0f, 0.0f);
@@ -1355,6 +1432,8 @@ int fsmod_structurealign(int argc, const char **argv) {
         std::vector<fshost_result *> pR(group);
         std::vector<int> Ls(group), ns(group), nres(group);
         std::vector<int64_t> ident(group);
+        std::vector<DecodedProfile> profA(profileQuery ? group : 0), prof3(profileQuery ? group : 0);
+        std::vector<fshost_profile_query> pqs(profileQuery ? group : 0);
         std::vector<char> line(1024 + 2 * 65536 * 2);
         for (;;) {
             const size_t b0 = next.fetch_add(group);
@@ -1366,12 +1445,23 @@ int fsmod_structurealign(int argc, const char **argv) {
                 if (data == dataEnd || *data == '\0') continue;
                 const int64_t qid = q3.idOf(queryKey);
                 if (qid < 0 || qA.idOf(queryKey) < 0) { if (!bad++) firstErr = "query key missing in query database"; break; }
-                const uint32_t L = q3.seqLen((size_t) qid);
-                if (qA.seqLen((size_t) qA.idOf(queryKey)) != L) { if (!bad++) firstErr = "query AA / 3Di entries do not match"; break; }
+                uint32_t L = 0;
+                if (profileQuery) {
+                    std::string perr;
+                    if (!prof3[m].decode(q3, (size_t) qid, perr) || !profA[m].decode(qA, (size_t) qA.idOf(queryKey), perr)) { if (!bad++) firstErr = perr; break; }
+                    L = (uint32_t) prof3[m].L;
+                    if (profA[m].L != prof3[m].L || L == 0) { if (!bad++) firstErr = "query AA / 3Di profiles do not match"; break; }
+                    pqs[m] = fshost_profile_query{profA[m].codes.data(), prof3[m].codes.data(), profA[m].fwd.data(), profA[m].rev.data(), prof3[m].fwd.data(), prof3[m].rev.data(), (int32_t) L, 0};
+                } else {
+                    L = q3.seqLen((size_t) qid);
+                    if (qA.seqLen((size_t) qA.idOf(queryKey)) != L) { if (!bad++) firstErr = "query AA / 3Di entries do not match"; break; }
+                }
                 if (ca.on && !ca.queryEntry(queryKey, caE[m], caL[m])) { if (!bad++) firstErr = "query key " + std::to_string(queryKey) + " has no C-alpha entry"; break; }
-                cA[m].resize(L); c3[m].resize(L);
-                const char *sA = qA.data((size_t) qA.idOf(queryKey)), *s3 = q3.data((size_t) qid);
-                for (uint32_t i = 0; i < L; i++) { cA[m][i] = mA.aa2num[(unsigned char) sA[i]]; c3[m][i] = m3.aa2num[(unsigned char) s3[i]]; }
+                if (!profileQuery) {
+                    cA[m].resize(L); c3[m].resize(L);
+                    const char *sA = qA.data((size_t) qA.idOf(queryKey)), *s3 = q3.data((size_t) qid);
+                    for (uint32_t i = 0; i < L; i++) { cA[m][i] = mA.aa2num[(unsigned char) sA[i]]; c3[m][i] = m3.aa2num[(unsigned char) s3[i]]; }
+                }
                 // prefilter entry: lines "targetKey \t score \t diagonal" (Util::parseKey, structurealign.cpp:351-355)
                 ids[m].clear();
                 while (data < dataEnd && *data != '\0') {
@@ -1394,7 +1484,8 @@ int fsmod_structurealign(int argc, const char **argv) {
             if (bad) break;
             if (m == 0) continue;
             if (ca.on) fshost_search_set_query_ca(s, (int) m, caE.data(), caL.data());
-            if (fshost_search_align_batch(s, (int) m, pA.data(), p3.data(), Ls.data(), ident.data(), pT.data(), ns.data(), pR.data(), nres.data()) != FSGPU_OK) {
+            if ((profileQuery ? fshost_search_align_batch_profile(s, (int) m, pqs.data(), ident.data(), pT.data(), ns.data(), pR.data(), nres.data())
+                              : fshost_search_align_batch(s, (int) m, pA.data(), p3.data(), Ls.data(), ident.data(), pT.data(), ns.data(), pR.data(), nres.data())) != FSGPU_OK) {
                 if (!bad++) firstErr = fshost_search_error(s);
                 break;
             }
@@ -1439,6 +1530,7 @@ int fsmod_structurerescorediagonal(int argc, const char **argv) {
     if (!qA.open(o.pos[0], err) || !q3.open(dbPathWithSuffix(o.pos[0], "_ss"), err) || !tA.open(o.pos[1], err) || !t3.open(dbPathWithSuffix(o.pos[1], "_ss"), err) ||
         !pref.open(o.pos[2], err))
         return fail(err);
+    if (isProfileDb(qA) || isProfileDb(q3)) return fail(profileRefusal("structurerescorediagonal", "which this module does not rescore"));
     const bool sameDB = o.pos[0] == o.pos[1];
     const bool includeIdentical = o.geti("--add-self-matches", 0) != 0;
     fshost_params par;

@@ -297,6 +297,33 @@ int fshost_search_prefilter_batch(fshost_search *s, int nq, const uint8_t *const
     return FSGPU_OK;
 }
 
+// profile queries: the pssm is the decoded alignment profile, the cap comes from its own bias (ssw_init's profile branch); no composition bias
+int fshost_search_prefilter_profile(fshost_search *s, const int8_t *pssm, int L, int64_t identityId, fsgpu_hit *hits) {
+    if (!s || !s->ctx || !pssm || L <= 0 || !hits) return FSGPU_E_ARG;
+    const double t0 = nowSec();
+    int nout = 0;
+    const int rc = fsgpu_gapless_scan(s->ctx, pssm, L, 255 - fshost_profile_bias(pssm, L), s->par.minDiagScoreThr, identityId, s->par.maxResListLen, hits, &nout);
+    s->stats[0] = 0; s->stats[1] = nowSec() - t0;
+    if (rc != FSGPU_OK) { s->err = fsgpu_last_error(s->ctx); return rc; }
+    return nout;
+}
+
+int fshost_search_prefilter_batch_profile(fshost_search *s, int nq, const int8_t *const *pssm, const int *L, const int64_t *identityId,
+                                          fsgpu_hit *hits, int *nhits) {
+    if (!s || !s->ctx || nq < 0 || (nq > 0 && (!pssm || !L || !hits || !nhits))) return FSGPU_E_ARG;
+    const double t0 = nowSec();
+    std::vector<fsgpu_gapless_query> gq(nq);
+    for (int i = 0; i < nq; i++) {
+        if (!pssm[i] || L[i] <= 0) return FSGPU_E_ARG;
+        gq[i].pssm = pssm[i]; gq[i].L = L[i]; gq[i].scoreCap = 255 - fshost_profile_bias(pssm[i], L[i]); gq[i].identityId = identityId ? identityId[i] : -1;
+    }
+    const double t1 = nowSec();
+    const int rc = fsgpu_gapless_scan_multi(s->ctx, gq.data(), nq, s->par.minDiagScoreThr, s->par.maxResListLen, hits, nhits);
+    s->stats[0] = t1 - t0; s->stats[1] = nowSec() - t1;
+    if (rc != FSGPU_OK) { s->err = fsgpu_last_error(s->ctx); return rc; }
+    return FSGPU_OK;
+}
+
 } // extern "C"
 
 // ---- helpers restating small reference functions -------------------------------------------------------------
@@ -344,6 +371,7 @@ struct AlignQuery {
     std::vector<int8_t> cbAA, cbSS, cbAAr, cbSSr;       // r: biases of the reversed query, indexed by reversed position
     double lambda = 0, mu = 0;
     const float *ca = nullptr;                          // x[L] y[L] z[L] when the LDDT filter is on
+    const fshost_profile_query *prof = nullptr;         // a profile query: scores come from its tables, qAA / q3di are its query letters, the biases are zero
 };
 
 // the four word profiles from codes + biases (StructureSmithWaterman.cpp:1566-1640: matrix column + position bias)
@@ -418,6 +446,68 @@ void pairBacktrace(const fshost_search *s, const AlignQuery &aq, uint32_t tid, c
     }
     blockBacktrace(s->matAA, s->mat3Di, aq.qAA, aq.q3di, aq.cbAA.data(), aq.cbSS.data(), aq.L, tAA.data(), t3Di.data(), Lt, f.qEnd, f.dbEnd,
                    f.score, par.gapOpen, par.gapExtend, bo);
+}
+
+// alignStartPosBacktrace (StructureSmithWaterman.cpp:540-739) with the score source as a parameter: what the sequence-query form
+// (fshost_search_startpos_backtrace) and the profile-query form (profileBacktrace) share.  pA / p3: the int16 word profiles of the REVERSED query
+// prefix [0, qEnd] (Lp = qEnd + 1 rows; pA NULL: 3Di only); the reverse pass against the reversed target prefix [0, dbEnd] runs on the device
+// (fsgpu_sw_batch_seqs: the first column that reaches the forward score is the start column, the smallest row holding it the start row).  bo.ok =
+// it reproduced `score`: the start cell is set.  trace(qStart, dbStart, tAA, t3Di, path) -- tAA / t3Di at position 0 of the target -- then decides
+// whether there is a cigar and makes it (banded_sw over the source's scores); identities are counted against qLetters (computerBacktrace, :746-773).
+// Uses the handle's context: the calling thread only.  Returns FSGPU_OK or < 0.
+template <class Trace>
+int startposBacktraceCore(fshost_search *s, uint32_t tid, int qEnd, int dbEnd, int score, const int16_t *pA, const int16_t *p3, const uint8_t *qLetters,
+                          Trace trace, BlockAlnOut &bo) {
+    const fshost_params &par = s->par;
+    const int Lp = qEnd + 1, Lt = dbEnd + 1;
+    bo = BlockAlnOut();
+    std::vector<uint8_t> tA(Lt), t3(Lt), fA(Lt), f3(Lt);
+    for (int k = 0; k < Lt; k++) {
+        uint8_t c = s->data3di[s->offsets[tid] + k]; c = c >= 32 ? c - 32 : c; f3[k] = c > 20 ? 20 : c;
+        uint8_t a = s->dataAA ? s->dataAA[s->offsets[tid] + k] : 20; a = a >= 32 ? a - 32 : a; fA[k] = a > 20 ? 20 : a;
+    }
+    for (int k = 0; k < Lt; k++) { t3[k] = f3[dbEnd - k]; tA[k] = fA[dbEnd - k]; }
+    const uint64_t offs[2] = {0, (uint64_t) Lt};
+    const int32_t lens[1] = {Lt};
+    fsgpu_swres f, r;
+    const int rc = fsgpu_sw_batch_seqs(s->ctx, pA, p3, pA, p3, Lp, tA.data(), t3.data(), offs, lens, 1, par.gapOpen, par.gapExtend, &f, &r);
+    if (rc != FSGPU_OK) { s->err = fsgpu_last_error(s->ctx); return rc; }
+    if (f.score != score) return FSGPU_OK;
+    bo.ok = true;
+    bo.qStart = qEnd - f.qEnd; bo.dbStart = dbEnd - f.dbEnd;
+    std::string path;
+    if (!trace(bo.qStart, bo.dbStart, fA.data(), f3.data(), path)) return FSGPU_OK;
+    int qp = bo.qStart, tp = bo.dbStart;
+    for (char c : path) {
+        if (c == 'M') { bo.identicalAA += fA[tp] == qLetters[qp]; qp++; tp++; }
+        else if (c == 'I') qp++;
+        else tp++;
+    }
+    bo.backtrace = path;
+    return FSGPU_OK;
+}
+
+// The profile-query form, which structurealign takes instead of the block aligner when isProfileSearch() (structurealign.cpp:91-100): the reversed
+// prefix comes from the tables, the trace-back runs over the tables, and when the coverage of [start, end] falls below covThr the reference returns
+// the start position without a cigar (:684-688).  A reverse pass that does not reproduce the score is an error (the reference exits there).
+int profileBacktrace(fshost_search *s, const AlignQuery &aq, uint32_t tid, const fsgpu_swres &f, BlockAlnOut &bo) {
+    const fshost_params &par = s->par;
+    const fshost_profile_query &pq = *aq.prof;
+    const int A = 21, L = aq.L, Lp = f.qEnd + 1, LtFull = s->lengths[tid];
+    if (f.qEnd < 0 || f.qEnd >= L || f.dbEnd < 0 || f.dbEnd >= LtFull) { s->err = "profile backtrace: bad end position"; return FSGPU_E_ARG; }
+    std::vector<int16_t> pA((size_t) A * Lp), p3((size_t) A * Lp);
+    for (int a = 0; a < A; a++)
+        for (int i = 0; i < Lp; i++) {
+            pA[(size_t) a * Lp + i] = (int16_t) pq.pAA[(size_t) a * L + f.qEnd - i];
+            p3[(size_t) a * Lp + i] = (int16_t) pq.p3Di[(size_t) a * L + f.qEnd - i];
+        }
+    const int rc = startposBacktraceCore(s, tid, f.qEnd, f.dbEnd, f.score, pA.data(), p3.data(), pq.codesAA,
+        [&](int qs, int ds, const uint8_t *tA, const uint8_t *t3, std::string &path) {
+            if (!hasCoverage(par.covThr, par.covMode, computeCov(qs, f.qEnd, L), computeCov(ds, f.dbEnd, LtFull))) return false;
+            return bandedBacktraceProfile(pq.pAA, pq.p3Di, L, qs, f.qEnd - qs + 1, tA + ds, t3 + ds, f.dbEnd - ds + 1, f.score, par.gapOpen, par.gapExtend, path);
+        }, bo);
+    if (rc == FSGPU_OK && !bo.ok) { s->err = "profile backtrace: score of forward / backward SW differ"; return FSGPU_E_ARG; }
+    return rc;
 }
 
 // the gates of alignStructure that come BEFORE the backtrace (structurealign.cpp:357-361 canBeCovered, :50-58 coverage and
@@ -654,7 +744,8 @@ int gateAlign(fshost_search *s, const AlignQuery &aq, int64_t identityId, const 
             bop = &pre[preIdx[k]];
         } else {
             const double tb0 = nowSec();
-            pairBacktrace(s, aq, tid, f, local);
+            if (aq.prof) { const int rc = profileBacktrace(s, aq, tid, f, local); if (rc != FSGPU_OK) return rc; }
+            else pairBacktrace(s, aq, tid, f, local);
             tBack += nowSec() - tb0;
             bop = &local;
         }
@@ -1059,6 +1150,83 @@ int fshost_search_align_batch(fshost_search *s, int nq, const uint8_t *const *qA
     return FSGPU_OK;
 }
 
+// The same for profile queries (fshost.h): no composition bias, mu / lambda from the 3Di profile's query letters, scores from the tables through
+// fsgpu_sw_multi_p / _dir_p, the same needsReversePass and gateAlign; the backtraces come from profileBacktrace inside gateAlign, one by one: each
+// starts with a device call on the handle's context, so the host pool's precomputation (precomputeBacktraces) is not used.
+int fshost_search_align_batch_profile(fshost_search *s, int nq, const fshost_profile_query *q, const int64_t *identityId,
+                                      const uint32_t *const *targetIds, const int *n, fshost_result *const *results, int *nres) {
+    if (!s || !s->ctx || nq < 0 || (nq > 0 && (!q || !targetIds || !n || !results || !nres))) return FSGPU_E_ARG;
+    const fshost_params &par = s->par;
+    if (par.altAlignment > 0) { s->err = "--alt-ali with a profile query is not supported"; return FSGPU_E_UNSUPPORTED; }
+    if (!(par.gapExtend >= 1 && par.gapOpen > par.gapExtend && par.gapOpen < 32768)) {
+        s->err = "gap costs must satisfy gapOpen > gapExtend >= 1 (got " + std::to_string(par.gapOpen) + " / " + std::to_string(par.gapExtend) + ")";
+        return FSGPU_E_UNSUPPORTED;
+    }
+    const double t0 = nowSec();
+    std::vector<AlignQuery> aq(nq);
+    std::vector<fsgpu_sw_pquery> dq(nq);
+    size_t total = 0;
+    for (int i = 0; i < nq; i++) {
+        if (!q[i].codesAA || !q[i].codes3Di || !q[i].pAA || !q[i].pAArev || !q[i].p3Di || !q[i].p3Direv || q[i].L <= 0 || n[i] < 0) return FSGPU_E_ARG;
+        for (int k = 0; k < q[i].L; k++) if (q[i].codesAA[k] > 20 || q[i].codes3Di[k] > 20) { s->err = "bad query residue code"; return FSGPU_E_ARG; }
+        AlignQuery &a = aq[i];
+        a.prof = &q[i]; a.qAA = q[i].codesAA; a.q3di = q[i].codes3Di; a.L = q[i].L;
+        s->evaluer.predictMuLambda(a.q3di, a.L, s->mat3Di.n, &a.lambda, &a.mu);
+        a.cbAA.assign(a.L, 0); a.cbSS.assign(a.L, 0); a.cbAAr.assign(a.L, 0); a.cbSSr.assign(a.L, 0);
+        dq[i].pAA_fwd = q[i].pAA; dq[i].p3Di_fwd = q[i].p3Di; dq[i].pAA_rev = q[i].pAArev; dq[i].p3Di_rev = q[i].p3Direv;
+        dq[i].L = q[i].L; dq[i].n = n[i]; dq[i].targetIds = targetIds[i];
+        total += (size_t) n[i];
+    }
+    { const int rcCa = lddtPrepareQueries(s, aq.data(), nq); if (rcCa != FSGPU_OK) return rcCa; }
+    s->fwd.resize(total); s->rev.assign(total, fsgpu_swres{0, 0, 0, 0});
+    const double t1 = nowSec();
+    const size_t onePassPairs = [] { const char *e = getenv("FSGPU_SW_ONEPASS_PAIRS"); return e ? (size_t) atoll(e) : (size_t) 16384; }();
+    int rc;
+    std::vector<std::vector<int32_t>> sel(nq);
+    const bool onePass = total > 0 && total <= onePassPairs;
+    rc = onePass ? fsgpu_sw_multi_p(s->ctx, dq.data(), nq, par.gapOpen, par.gapExtend, s->fwd.data(), s->rev.data())
+                 : fsgpu_sw_multi_dir_p(s->ctx, dq.data(), nq, par.gapOpen, par.gapExtend, 0, nullptr, nullptr, s->fwd.data());
+    if (rc != FSGPU_OK) { s->err = fsgpu_last_error(s->ctx); return rc; }
+    size_t b = 0, any = 0;
+    for (int i = 0; i < nq; i++) {
+        for (int k = 0; k < n[i]; k++) {
+            const uint32_t tid = targetIds[i][k];
+            if (tid >= s->keys.size()) { s->err = "target id out of range"; return FSGPU_E_ARG; }
+            if (needsReversePass(s, aq[i], tid, s->fwd[b + k])) { sel[i].push_back(k); any++; }
+            else s->rev[b + k] = fsgpu_swres{0, 0, 0, 0};      // what the two-pass form leaves for pairs structurealign never reverses
+        }
+        b += (size_t) n[i];
+    }
+    s->stats[7] = (double) any;
+    if (!onePass && any) {
+        std::vector<const int32_t *> selp(nq);
+        std::vector<int32_t> nsel(nq);
+        for (int i = 0; i < nq; i++) { selp[i] = sel[i].data(); nsel[i] = (int32_t) sel[i].size(); }
+        rc = fsgpu_sw_multi_dir_p(s->ctx, dq.data(), nq, par.gapOpen, par.gapExtend, 1, selp.data(), nsel.data(), s->rev.data());
+        if (rc != FSGPU_OK) { s->err = fsgpu_last_error(s->ctx); return rc; }
+    }
+    const double t2 = nowSec();
+    double tBack = 0;
+    s->cigars.clear();
+    size_t base = 0;
+    for (int i = 0; i < nq; i++) {
+        nres[i] = gateAlign(s, aq[i], identityId ? identityId[i] : -1, targetIds[i], n[i], s->fwd.data() + base, s->rev.data() + base, results[i], tBack, nullptr, nullptr);
+        if (nres[i] < 0) return nres[i];
+        base += (size_t) n[i];
+    }
+    s->stats[2] = t1 - t0; s->stats[3] = t2 - t1; s->stats[5] = tBack; s->stats[4] = nowSec() - t2 - tBack;
+    s->lastDeviceBt = 0; s->lastBtTasks = 0;
+    return FSGPU_OK;
+}
+
+// one profile query: the batch body with one member (the same device entries, the same accept loop)
+int fshost_search_align_profile(fshost_search *s, const fshost_profile_query *q, int64_t identityId, const uint32_t *targetIds, int n, fshost_result *results) {
+    if (!q || n < 0 || (n > 0 && !targetIds) || !results) return FSGPU_E_ARG;
+    int nres = 0;
+    const int rc = fshost_search_align_batch_profile(s, 1, q, &identityId, &targetIds, &n, &results, &nres);
+    return rc != FSGPU_OK ? rc : nres;
+}
+
 // The exhaustive search (StructureSearch.cpp:114-127: no prefilter, `fake_pref` hands every target to structurealign) for nq queries: alignStructure's first
 // e-value gate as a score cutoff per query, ONE database-wide forward pass that selects against it on the device (fsgpu_sw_scan_c), and the
 // survivors -- in ascending target index, the order of fake_pref's lines -- through fshost_search_align_batch unchanged.  That body computes the forward
@@ -1315,7 +1483,7 @@ int fshost_search_startpos_backtrace(fshost_search *s, const uint8_t *qAA, const
     int rc = prepareAlign(s, aq, s->rAA, s->r3Di);                 // forward profiles give the rounded biases cbAA / cbSS
     if (rc != FSGPU_OK) return rc;
     // reversed query prefix [0, qEnd] with its position biases (createQueryProfile on query_*_rev_sequence + queryOffset, :617-620)
-    const int Lp = qEnd + 1, Lt = dbEnd + 1;
+    const int Lp = qEnd + 1;
     std::vector<int16_t> pA((size_t) A * Lp), p3((size_t) A * Lp);
     for (int a = 0; a < A; a++)
         for (int i = 0; i < Lp; i++) {
@@ -1323,37 +1491,19 @@ int fshost_search_startpos_backtrace(fshost_search *s, const uint8_t *qAA, const
             pA[(size_t) a * Lp + i] = (int16_t) (s->matAA.tiny[(size_t) a * A + qAA[src]] + aq.cbAA[src]);
             p3[(size_t) a * Lp + i] = (int16_t) (s->mat3Di.tiny[(size_t) a * A + q3di[src]] + aq.cbSS[src]);
         }
-    std::vector<uint8_t> tA(Lt), t3(Lt), fA(Lt), f3(Lt);
-    for (int k = 0; k < Lt; k++) {
-        uint8_t c = s->data3di[s->offsets[targetId] + k]; c = c >= 32 ? c - 32 : c; f3[k] = c > 20 ? 20 : c;
-        uint8_t a = s->dataAA ? s->dataAA[s->offsets[targetId] + k] : 20; a = a >= 32 ? a - 32 : a; fA[k] = a > 20 ? 20 : a;
-    }
-    for (int k = 0; k < Lt; k++) { t3[k] = f3[dbEnd - k]; tA[k] = fA[dbEnd - k]; }
-    const uint64_t offs[2] = {0, (uint64_t) Lt};
-    const int32_t lens[1] = {Lt};
-    fsgpu_swres f, r;
-    rc = fsgpu_sw_batch_seqs(s->ctx, useAA ? pA.data() : nullptr, p3.data(), useAA ? pA.data() : nullptr, p3.data(), Lp, tA.data(), t3.data(), offs, lens, 1,
-                             par.gapOpen, par.gapExtend, &f, &r);
-    if (rc != FSGPU_OK) { s->err = fsgpu_last_error(s->ctx); return rc; }
-    if (f.score != score) return 0;
-    const int qs = qEnd - f.qEnd, ds = dbEnd - f.dbEnd;
-    *qStart = qs; *dbStart = ds;
-    std::string path;
-    const int qLen = qEnd - qs + 1, dbLen = dbEnd - ds + 1;
-    if (!bandedBacktrace(s->matAA, s->mat3Di, qAA + qs, q3di + qs, aq.cbAA.data() + qs, aq.cbSS.data() + qs, qLen, fA.data() + ds, f3.data() + ds, dbLen,
-                         score, par.gapOpen, par.gapExtend, path))
-        return 0;
-    // computerBacktrace (:746-773)
-    unsigned int ids = 0;
-    int qp = qs, tp = ds;
-    for (char c : path) {
-        if (c == 'M') { ids += fA[tp] == qAA[qp]; qp++; tp++; }
-        else if (c == 'I') qp++;
-        else tp++;
-    }
-    if (identicalAA) *identicalAA = ids;
-    if (path.size() + 1 > btCap) { s->err = "startpos_backtrace: backtrace buffer too small"; return FSGPU_E_ARG; }
-    memcpy(backtrace, path.c_str(), path.size() + 1);
+    BlockAlnOut bo;
+    rc = startposBacktraceCore(s, targetId, qEnd, dbEnd, score, useAA ? pA.data() : nullptr, p3.data(), qAA,
+        [&](int qs, int ds, const uint8_t *tA, const uint8_t *t3, std::string &path) {
+            return bandedBacktrace(s->matAA, s->mat3Di, qAA + qs, q3di + qs, aq.cbAA.data() + qs, aq.cbSS.data() + qs, qEnd - qs + 1, tA + ds, t3 + ds, dbEnd - ds + 1,
+                                   score, par.gapOpen, par.gapExtend, path);
+        }, bo);
+    if (rc != FSGPU_OK) return rc;
+    if (!bo.ok) return 0;
+    *qStart = bo.qStart; *dbStart = bo.dbStart;
+    if (bo.backtrace.empty()) return 0;
+    if (identicalAA) *identicalAA = bo.identicalAA;
+    if (bo.backtrace.size() + 1 > btCap) { s->err = "startpos_backtrace: backtrace buffer too small"; return FSGPU_E_ARG; }
+    memcpy(backtrace, bo.backtrace.c_str(), bo.backtrace.size() + 1);
     return 1;
 }
 

@@ -365,17 +365,14 @@ struct Sw3ImgQuery {
     uint16_t R, HL;
 };
 
-#ifdef FS_SW3_DEFINE_IMAGE_KERNEL        // one definition: fsgpu_sw3.hip, 3Di-only build
-__global__ __launch_bounds__(256) void k_sw3_image(const Sw3ImgQuery *qs, const uint8_t *data, const int8_t *mat3, const int8_t *matA, uint32_t *img, int hasAA) {
-    __shared__ int8_t m[2][kAlphabet * kAlphabet];
-    for (int i = threadIdx.x; i < kAlphabet * kAlphabet; i += blockDim.x) { m[0][i] = mat3[i]; m[1][i] = hasAA ? matA[i] : (int8_t) 0; }
-    __syncthreads();
-    const Sw3ImgQuery q = qs[blockIdx.y];
+// The gather both builders share: score(dir, tbl, a, row) is the entry of (direction, table, letter a, query row < L); everything else -- the
+// plane layout, the copies of the remainder plane, row 21 -- is the image format k_sw3 reads and must not depend on where the scores come from.
+template <class Score>
+__device__ __forceinline__ void sw3ImageBody(const Sw3ImgQuery &q, uint32_t *img, int hasAA, Score score) {
     const int R = q.R, HL = q.HL, L = (int) q.L, D = sw3Dw(R), nt = hasAA ? 2 : 1;
     const int rowDw = sw3RowBytes(R, HL) / 4;
     const int perTable = kSw2Rows * HL * D;
     const int total = 2 * nt * perTable;
-    const uint8_t *d = data + q.dataOff;
     for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
         const int dt = idx / perTable;                 // direction * nt + table
         const int dir = dt / nt, tbl = dt - dir * nt;
@@ -386,15 +383,10 @@ __global__ __launch_bounds__(256) void k_sw3_image(const Sw3ImgQuery *qs, const 
         uint32_t v = 0;
         if (a == kAlphabet) v = tbl == 0 ? 0x80008000u : 0u;
         else {
-            const uint8_t *codes = d + (size_t) tbl * L;
-            const int8_t *cb = (const int8_t *) d + (size_t) (2 + 2 * dir + tbl) * L;
 #pragma unroll
             for (int h = 0; h < 2; h++) {
                 const int r = 2 * j + h, row = l * R + r;
-                if (r < R && row < L) {
-                    const int sc = (int) m[tbl][a * kAlphabet + codes[dir ? L - 1 - row : row]] + (int) cb[row];
-                    v |= (uint32_t) (uint16_t) (int16_t) sc << (16 * h);
-                }
+                if (r < R && row < L) v |= (uint32_t) (uint16_t) (int16_t) score(dir, tbl, a, row) << (16 * h);
             }
         }
         uint32_t *dst = img + q.imgOff + (size_t) dt * kSw2Rows * rowDw + (size_t) a * rowDw;
@@ -405,6 +397,34 @@ __global__ __launch_bounds__(256) void k_sw3_image(const Sw3ImgQuery *qs, const 
             for (int c = 1; c < nc; c++) dst[di + c * st] = v;
         }
     }
+}
+
+#ifdef FS_SW3_DEFINE_IMAGE_KERNEL        // one definition: fsgpu_sw3.hip, 3Di-only build
+__global__ __launch_bounds__(256) void k_sw3_image(const Sw3ImgQuery *qs, const uint8_t *data, const int8_t *mat3, const int8_t *matA, uint32_t *img, int hasAA) {
+    __shared__ int8_t m[2][kAlphabet * kAlphabet];
+    for (int i = threadIdx.x; i < kAlphabet * kAlphabet; i += blockDim.x) { m[0][i] = mat3[i]; m[1][i] = hasAA ? matA[i] : (int8_t) 0; }
+    __syncthreads();
+    const Sw3ImgQuery q = qs[blockIdx.y];
+    const int L = (int) q.L;
+    const uint8_t *d = data + q.dataOff;
+    sw3ImageBody(q, img, hasAA, [&](int dir, int tbl, int a, int row) {
+        const uint8_t *codes = d + (size_t) tbl * L;
+        const int8_t *cb = (const int8_t *) d + (size_t) (2 + 2 * dir + tbl) * L;
+        return (int) m[tbl][a * kAlphabet + codes[dir ? L - 1 - row : row]] + (int) cb[row];
+    });
+}
+
+// k_sw3_image_profile -- the same images for PROFILE queries (DBTYPE_HMM_PROFILE: the later rounds of an iterative search).  The alignment
+// profile of such a query is its own table (Sequence::mapProfile: profile_score / 4, [letter][position], X row 0) and
+// StructureSmithWaterman::ssw_init takes it as it is: no matrix, no composition bias.  data of query i at qs[i].dataOff: the int8 tables
+// [3Di forward][AA forward][3Di reversed][AA reversed] (without AA: [3Di forward][3Di reversed]), 21 x L each, [a * L + row]; the reversed
+// tables are indexed by the position in the reversed query, as the caller made them.  A plain gather: neighbouring threads read neighbouring
+// bytes of one letter's row and write the dwords k_sw3_image writes, so nothing k_sw3 sees -- addresses, banks, row 21 -- differs.
+__global__ __launch_bounds__(256) void k_sw3_image_profile(const Sw3ImgQuery *qs, const int8_t *data, uint32_t *img, int hasAA) {
+    const Sw3ImgQuery q = qs[blockIdx.y];
+    const int L = (int) q.L, nt = hasAA ? 2 : 1;
+    const int8_t *d = data + q.dataOff;
+    sw3ImageBody(q, img, hasAA, [&](int dir, int tbl, int a, int row) { return (int) d[((size_t) (dir * nt + tbl) * kAlphabet + a) * L + row]; });
 }
 #endif
 

@@ -258,6 +258,23 @@ int fsgpu_sw_multi_dir_c(fsgpu_ctx *ctx, const int8_t *mat3Di, const int8_t *mat
  * host between two passes.  fwd / rev as in fsgpu_sw_multi. */
 int fsgpu_sw_multi_c(fsgpu_ctx *ctx, const int8_t *mat3Di, const int8_t *matAA, const fsgpu_sw_cquery *q, int nq, int gapOpen, int gapExtend,
                      fsgpu_swres *fwd, fsgpu_swres *rev);
+/* The same for PROFILE queries (a query database of type DBTYPE_HMM_PROFILE: every round of `search --num-iterations` after the first).
+ * The alignment profile of such a query is its own table -- Sequence::mapProfile's profile_score / 4, [letter][position], X row 0
+ * (fshost_profile_decode) -- and StructureSmithWaterman::ssw_init takes it as it is (StructureSmithWaterman.cpp:1586-1660: no matrix, no
+ * composition bias, word and int profiles are the table widened).  p*[a * L + i], a in 0..20, int8; the _rev tables are the profile reversed
+ * position by position.  pAA_* NULL for --alignment-type 0: either all queries of a call carry them or none.  Results, selection, the
+ * int16 -> int32 re-run, fsgpu_sw3_last_plan and the gap-cost rule are those of fsgpu_sw_multi_dir_c / fsgpu_sw_multi_c: queries of up
+ * to 1024 positions run through the same k_sw3 launches over images built from the tables (k_sw3_image_profile), longer ones are widened
+ * to int16 on the host and take fsgpu_sw_multi_dir.  The images a context keeps are keyed by every byte of the tables. */
+typedef struct {
+    const int8_t *pAA_fwd, *p3Di_fwd, *pAA_rev, *p3Di_rev;
+    int32_t L;
+    int32_t n;
+    const uint32_t *targetIds;
+} fsgpu_sw_pquery;
+int fsgpu_sw_multi_dir_p(fsgpu_ctx *ctx, const fsgpu_sw_pquery *q, int nq, int gapOpen, int gapExtend, int dir,
+                         const int32_t *const *sel, const int32_t *nsel, fsgpu_swres *out);
+int fsgpu_sw_multi_p(fsgpu_ctx *ctx, const fsgpu_sw_pquery *q, int nq, int gapOpen, int gapExtend, fsgpu_swres *fwd, fsgpu_swres *rev);
 /* Exhaustive search (Foldseek's --exhaustive-search 1 / search --prefilter-mode 2: no prefilter, every target goes to structurealign,
  * F/src/workflow/StructureSearch.cpp:114-127): the forward pass of every query against EVERY target of the database, selected on the device against
  * a score cutoff per query (fshost_evalue_score_cutoff: alignStructure's first e-value gate, structurealign.cpp:55-59).
@@ -541,7 +558,7 @@ void fsgpu_history_counters(const fsgpu_ctx *ctx, uint64_t *out8);
  * k_sw2 launches (HIP events on the context stream; -1 when the pass did not run), DP cells (query rows x target columns over the
  * single-tile pairs), pairs, and the VALU wave-instructions its waves issue (DP rows + per-step overhead; the issue-rate roofline's unit). */
 void fsgpu_sw_last_passes(const fsgpu_ctx *ctx, double *out);
-/* out[12]: what the last fsgpu_sw_multi_dir_c / fsgpu_sw_multi_c call of this context planned and ran (counters kept on the host; a call that
+/* out[12]: what the last fsgpu_sw_multi_dir_c / fsgpu_sw_multi_c (or _dir_p / _p) call of this context planned and ran (counters kept on the host; a call that
  * fails its argument checks leaves them as they were; one that fails later, out of memory for instance, leaves them zeroed or partly filled).  A pair counts once, also when fsgpu_sw_multi_c runs it in both directions.
  * [0] [1] [2] pairs run by k_sw3 with 16 / 32 / 64 lanes per target pair; [3] [4] [5] for the same three shapes the rows-per-lane classes that
  * were launched, bit R set for R rows per lane (R = 1..24 with 16 lanes, 1..16 with 32 and 64); [6] pairs of the queries of more than 1024 rows,

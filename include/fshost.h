@@ -155,6 +155,28 @@ int fshost_search_align(fshost_search *s, const uint8_t *qAA, const uint8_t *q3d
 int fshost_search_align_batch(fshost_search *s, int nq, const uint8_t *const *qAA, const uint8_t *const *q3di, const int *L,
                               const int64_t *identityId, const uint32_t *const *targetIds, const int *n,
                               fshost_result *const *results, int *nres);
+/* The two bodies for PROFILE queries (entries of a DBTYPE_HMM_PROFILE database, decoded by fshost_profile_decode).
+ * Prefilter (ungappedprefilter.cpp:381-384 with a profile Sequence): the pssm is the 3Di alignment profile itself, the cap 255 - fshost_profile_bias;
+ * no composition bias whatever the handle's parameters say.  Arguments and results as fshost_search_prefilter_batch with pssm[q] = int8 [21 * L[q]].
+ * Align (structurealign.cpp:37-112 with isProfileSearch()): the same gates, order and limits as fshost_search_align_batch; mu / lambda from the 3Di
+ * profile's query letters; forward and reversed scores from the tables as they are (fsgpu_sw_multi_p / _dir_p), BOTH tables whatever alignmentType is
+ * (the reference scales only the AA MATRIX by --alignment-type, and a profile query does not read it); start position, backtrace and identity count of
+ * an accepted hit from alignStartPosBacktrace<PROFILE> (the reverse pass on the device, the banded trace-back over the tables on the host; without a
+ * backtrace when the coverage of the start-to-end range falls below covThr) instead of the block aligner.  altAlignment > 0 is refused
+ * (FSGPU_E_UNSUPPORTED).  A profile query database has no _ca of its own; with C-alpha data bound, LDDT / TM-score of a hit go through the per-hit path. */
+typedef struct {
+    const uint8_t *codesAA, *codes3Di;          /* query letters of the two profiles (Sequence::numSequence) */
+    const int8_t *pAA, *pAArev, *p3Di, *p3Direv; /* [21 * L] each */
+    int32_t L;
+    int32_t reserved;
+} fshost_profile_query;
+/* one query: counterparts of fshost_search_prefilter (returns the number of hits) and fshost_search_align (returns the number of accepted alignments) */
+int fshost_search_prefilter_profile(fshost_search *s, const int8_t *pssm, int L, int64_t identityId, fsgpu_hit *hits);
+int fshost_search_align_profile(fshost_search *s, const fshost_profile_query *q, int64_t identityId, const uint32_t *targetIds, int n, fshost_result *results);
+int fshost_search_prefilter_batch_profile(fshost_search *s, int nq, const int8_t *const *pssm, const int *L, const int64_t *identityId,
+                                          fsgpu_hit *hits, int *nhits);
+int fshost_search_align_batch_profile(fshost_search *s, int nq, const fshost_profile_query *q, const int64_t *identityId,
+                                      const uint32_t *const *targetIds, const int *n, fshost_result *const *results, int *nres);
 /* Exhaustive search (--exhaustive-search 1 / search --prefilter-mode 2, F/src/workflow/StructureSearch.cpp:114-127: no prefilter, every target goes to
  * structurealign): per query mu / lambda and the score cutoff of alignStructure's first e-value gate (fshost_evalue_score_cutoff at the handle's evalThr),
  * one database-wide forward pass with the selection on the device (fsgpu_sw_scan_c), and the survivors, in ascending target index, through the body of
@@ -238,6 +260,25 @@ int fshost_block_backtrace(const fshost_matrix *mAA, const fshost_matrix *m3Di, 
 int fshost_banded_backtrace(const fshost_matrix *mAA, const fshost_matrix *m3Di, const uint8_t *qAA, const uint8_t *q3Di, const int8_t *cbAA,
                             const int8_t *cbSS, const uint8_t *tAA, const uint8_t *t3Di, int qStart, int qEnd, int dbStart, int dbEnd, int score,
                             int gapOpen, int gapExtend, unsigned int *identicalAA, char *backtrace, size_t btCap);
+
+/* ---- profile queries: an entry of a DBTYPE_HMM_PROFILE database (result2profile's output; M/src/commons/Sequence.cpp:301-340 mapProfile) ----
+ * An entry is L records of FSHOST_PROFILE_RECORD bytes: 20 score bytes (int8), the query letter, the consensus letter, neff and two gap bytes the
+ * reference build does not read (GAP_POS_SCORING is off).  len: the bytes of the records, WITHOUT the entry's terminator (index length - 1).
+ * codes[L] receives the query letters (Sequence::numSequence: what the e-value network is fed), consensus[L] the consensus letters, profile[21 * L]
+ * the alignment profile [letter][position] = score / 4 (C division, towards zero: -128 -> -32, 127 -> 31, -3 -> 0) with the X row 0, profileRev the
+ * same reversed position by position (the reversed query of structurealign.cpp:345-347).  Any output may be NULL.  Returns L (0 for an empty
+ * entry), or a negative code with the reason in err (errCap bytes, may be NULL): FSHOST_PROFILE_E_LENGTH when len is no multiple of the record size
+ * or holds more than FSGPU_MAX_SEQ_LEN positions, FSHOST_PROFILE_E_LETTER when a query or consensus letter is above 20 (the reference would index
+ * past its tables); nothing is written then. */
+#define FSHOST_PROFILE_RECORD 25
+#define FSHOST_PROFILE_E_ARG (-1)
+#define FSHOST_PROFILE_E_LENGTH (-2)
+#define FSHOST_PROFILE_E_LETTER (-3)
+int fshost_profile_decode(const char *entry, size_t len, uint8_t *codes, uint8_t *consensus, int8_t *profile, int8_t *profileRev, char *err, size_t errCap);
+/* The bias of the profile branch of SmithWaterman::ssw_init (StripedSmithWaterman.cpp:1397-1406): minus the smallest of the 20 x L scores, 0 when none
+ * is negative; there is no composition bias.  The gapless scan of a profile query (ungappedprefilter.cpp:381-384) runs with this pssm and the score
+ * cap 255 - bias. */
+int fshost_profile_bias(const int8_t *profile, int L);
 
 /* ---- C-alpha coordinates and LDDT (F/src/commons/Coordinate16.h, LDDT.{h,cpp}) ----
  * fshost_ca_decode == Coordinate16::read: a <db>_ca entry of entryLen bytes for a chain of L residues -> out = x[L] y[L] z[L].  An entry of at least
