@@ -93,8 +93,10 @@ def start_cell(p3, pA, t3, tA, q_end, db_end, score, go=10, ge=1):
     return q_end - int(r["qEnd"]), db_end - int(r["dbEnd"])
 
 
-def banded_path(match, q_len, db_len, score, go=10, ge=1):
+def banded_path(match, q_len, db_len, score, go=10, ge=1, doublings=None, edge_slot=True):
     """banded_sw's M / I / D string (start -> end) of a q_len x db_len rectangle; match: int32 [q_len, db_len] substitution scores.  None: trace back error.
+    doublings: a list that receives every band width the loop had to double.  edge_slot=False: WITHOUT the slot quirk described below -- not what the
+    source does; it exists so that a test can name the rectangles whose path the quirk decides.
     Stated in (row, column) terms.  What the source's band slots amount to: a cell outside the band of the row above reads as H = E = 0, as does the
     cell left of a row's band, F starts every row at 0 -- and one more thing, `h_b[edge] = e_b[edge] = 0` with edge = end + 1 taken as a SLOT (:1783-1784):
     while the band still starts at column 0, that slot is the column `end` of the row above, so once `end` is clamped to the last column the row
@@ -107,7 +109,7 @@ def banded_path(match, q_len, db_len, score, go=10, ge=1):
         rows, best = [], 0
         for i in range(q_len):
             beg, end = max(0, i - band), min(db_len - 1, i + band)
-            if 1 <= i <= band + 1 and end == db_len - 1 and db_len - 1 <= i - 1 + band:
+            if edge_slot and 1 <= i <= band + 1 and end == db_len - 1 and db_len - 1 <= i - 1 + band:
                 Hp[end] = 0; Ep[end] = 0
             j = cols[beg:end + 1]
             n = len(j)
@@ -140,6 +142,8 @@ def banded_path(match, q_len, db_len, score, go=10, ge=1):
             rows.append((beg, end, (de, df, dh)))
         if best >= score:
             break
+        if doublings is not None:
+            doublings.append(band)
         band *= 2
     i, j, state, ops = q_len - 1, db_len - 1, 2, []
     while i > 0 or j > 0:
