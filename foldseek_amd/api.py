@@ -145,6 +145,7 @@ def lib():
         "fsgpu_gapless_plan_items": (i64, [vp, C.c_uint32, i32, f64, vp, u64, vp]),
         "fsgpu_gapless_item_records": (i64, [vp, u64, vp, vp, C.c_uint32, vp]),
         "fsgpu_gapless_pair_halves": (i32, [vp, i32, vp, vp, vp]),
+        "fsgpu_gapless_shape": (i32, [i32, C.POINTER(i32), C.POINTER(i32)]),
         "fsgpu_db_broadcast": (i32, [vp, C.POINTER(vp), i32, C.POINTER(i32)]),
         "fsgpu_rccl_selfcheck": (i32, [vp]),
         "fsgpu_stream": (vp, [vp]),
@@ -252,7 +253,7 @@ def exported_symbols():
     return ["fsgpu_create", "fsgpu_destroy", "fsgpu_last_error", "fsgpu_device", "fsgpu_stream", "fsgpu_db_load",
             "fsgpu_db_adopt_device", "fsgpu_db_check_table", "fsgpu_db_size", "fsgpu_db_residues", "fsgpu_gapless_scan", "fsgpu_gapless_scores",
             "fsgpu_gapless_launch", "fsgpu_gapless_finish", "fsgpu_sw_batch", "fsgpu_sw_multi", "fsgpu_sw_multi_dir", "fsgpu_sw_multi_dir_c", "fsgpu_sw_multi_c", "fsgpu_sw_multi_dir_p", "fsgpu_sw_multi_p", "fsgpu_sw_launch", "fsgpu_sw_finish",
-            "fsgpu_db_broadcast", "fsgpu_rccl_selfcheck", "fsgpu_device_count", "fsgpu_live_devices", "fsgpu_gapless_plan_items", "fsgpu_gapless_item_records", "fsgpu_gapless_pair_halves", "fsgpu_block_backtrace", "fsgpu_block_backtrace_footprint",
+            "fsgpu_db_broadcast", "fsgpu_rccl_selfcheck", "fsgpu_device_count", "fsgpu_live_devices", "fsgpu_gapless_plan_items", "fsgpu_gapless_item_records", "fsgpu_gapless_pair_halves", "fsgpu_gapless_shape", "fsgpu_block_backtrace", "fsgpu_block_backtrace_footprint",
             "fsgpu_lddt_batch", "fsgpu_tm_batch", "fsgpu_tm_superpose_batch", "fsgpu_last_kernel_ms", "fsgpu_history_counters", "fsgpu_sw_last_passes", "fsgpu_sw3_last_plan", "fsgpu_kmer_index_build", "fsgpu_kmer_index_entries", "fsgpu_kmer_index_entry_bytes", "fsgpu_kmer_index_get_params", "fsgpu_kmer_search",
             "fsgpu_kmer_index_copy", "fsgpu_kmer_row_copy", "fsgpu_kmer_last_counts", "fsgpu_kmer_last_segments", "fsgpu_kmer_plan_coarse", "fsgpu_kmer_batch_hint",
             "fsgpu_diag_rescore", "fsgpu_sw_batch_seqs", "fsgpu_sw_scan_c", "fsgpu_sw_scan_last"]
@@ -269,6 +270,14 @@ def db_check_table(offsets, lengths, nbytes):
     if len(off) != len(ln) + 1:
         raise FsgpuError("offsets must have one entry more than lengths")
     return int(lib().fsgpu_db_check_table(_ptr(off), _ptr(ln), len(ln), int(nbytes)))
+
+
+def gapless_shape(L):
+    """fsgpu_gapless_shape (host only): (row tiles, registers per lane R) of a query of L residues in the gapless scan"""
+    n_tiles, R = C.c_int(0), C.c_int(0)
+    if lib().fsgpu_gapless_shape(int(L), C.byref(n_tiles), C.byref(R)) != 0:
+        raise FsgpuError(f"fsgpu_gapless_shape: no query of {L} residues")
+    return n_tiles.value, R.value
 
 
 class Matrix:

@@ -189,8 +189,10 @@ using GaplessLaunchFn = int (*)(fsgpu_ctx *, const GaplessArgs &);
                                launchGapless<M * (B + 5), __VA_ARGS__>, launchGapless<M * (B + 6), __VA_ARGS__>, launchGapless<M * (B + 7), __VA_ARGS__>, launchGapless<M * (B + 8), __VA_ARGS__>
 static const GaplessLaunchFn kGaplessUntiled[kGaplessMaxRUntiled + 1] = {nullptr, FS_GAPLESS8(1, 0, false), FS_GAPLESS8(1, 8, false), FS_GAPLESS8(1, 16, false), FS_GAPLESS8(1, 24, false),
                                                                         FS_GAPLESS8(1, 32, false), FS_GAPLESS8(1, 40, false), FS_GAPLESS8(1, 48, false)};
-// query row tiles: more than one tile means L > 896, so a tile has more than 256 rows: R = 17..32
-static const GaplessLaunchFn kGaplessTiled[16] = {FS_GAPLESS8(1, 16, true), FS_GAPLESS8(1, 24, true)};
+// query row tiles: more than one tile means L > 896, and gaplessShape cuts tiles of equal height: two of 449..512 rows (R = 29..32), three of
+// 342..512 (R = 22..32), four or more of at least 385 (R >= 25).  R = 22..32 are all the counts a length can reach (tests walk every L).
+constexpr int kGaplessTiledMinR = 22;
+static const GaplessLaunchFn kGaplessTiled[kGaplessMaxR - kGaplessTiledMinR + 1] = {launchGapless<22, true>, launchGapless<23, true>, launchGapless<24, true>, FS_GAPLESS8(1, 24, true)};
 // two short queries of class R = 1..16 in one kernel of 2 R registers
 static const GaplessLaunchFn kGaplessPaired[kGaplessMaxR / 2 + 1] = {nullptr, FS_GAPLESS8(2, 0, false, true), FS_GAPLESS8(2, 8, false, true)};
 // two queries of class R = 17..36 in the halves of every register, R registers
@@ -199,6 +201,21 @@ static const GaplessLaunchFn kGaplessHalves[kGaplessHalvesMaxR - kGaplessHalvesM
                                                                                            launchGapless<35, false, false, true>, launchGapless<36, false, false, true>};
 #undef FS_GAPLESS8
 static_assert(kGaplessHalvesMinR == 17 && kGaplessHalvesMaxR == 36, "kGaplessHalves lists the classes 17..36");
+
+// The shape of a query of L rows: up to 16 * kGaplessMaxRUntiled rows in one piece, R = ceil(L / 16) registers (16-row granularity); beyond that
+// row tiles of at most 512 rows and equal height: L = 1025 runs as 3 x 352 rows (R = 22), not as 512 + 512 + 1 rows at the full R = 32 cost each.
+// Pure host function, exported as fsgpu_gapless_shape for the CPU tests.
+static void gaplessShape(int L, int *nTiles, int *R) {
+    const int rows = (L + 15) / 16;                       // rows per strip per lane
+    *nTiles = L <= 16 * kGaplessMaxRUntiled ? 1 : (L + 16 * kGaplessMaxR - 1) / (16 * kGaplessMaxR);
+    *R = *nTiles > 1 ? ((L + *nTiles - 1) / *nTiles + 15) / 16 : std::max(1, rows);
+}
+
+extern "C" int fsgpu_gapless_shape(int L, int *nTiles, int *R) {
+    if (L < 1 || L > FSGPU_MAX_SEQ_LEN || !nTiles || !R) return -1;
+    gaplessShape(L, nTiles, R);
+    return 0;
+}
 
 // hits in the reference's order (hit_t::compareHitsByScoreAndId; scores are non-negative here)
 static void emitHits(fsgpu_hit *out, const uint32_t *ids, const int32_t *scores, uint32_t m) {
@@ -479,11 +496,8 @@ int fsgpu_gapless_launch(fsgpu_ctx *ctx, const int8_t *pssm, int L, int scoreCap
     if (!pssm || L <= 0 || L > FSGPU_MAX_SEQ_LEN || maxRes <= 0) { ctx->err = "fsgpu_gapless_launch: bad argument"; return FSGPU_E_ARG; }
     if (!ctx->db || ctx->db->n == 0) { ctx->err = "no database loaded"; return FSGPU_E_NODB; }
     if (ctx->gaplessPending) { ctx->err = "previous gapless scan not finished"; return FSGPU_E_ARG; }
-    const int rows = (L + 15) / 16;                       // rows per strip per lane
-    // up to 16 * kGaplessMaxRUntiled rows in one piece; beyond that row tiles of at most 512 rows and equal height: L = 1025 runs as
-    // 3 x 352 rows (R = 22), not as 512 + 512 + 1 rows at the full R = 32 cost each
-    const int nTiles = L <= 16 * kGaplessMaxRUntiled ? 1 : (L + 16 * kGaplessMaxR - 1) / (16 * kGaplessMaxR);
-    const int R = nTiles > 1 ? ((L + nTiles - 1) / nTiles + 15) / 16 : std::max(1, rows);
+    int nTiles, R;
+    gaplessShape(L, &nTiles, &R);
     HIPCHK(hipSetDevice(ctx->device));
     const uint32_t n = (uint32_t) ctx->db->n;
     const uint32_t nChunks = (n + kSelChunk - 1) / kSelChunk;
@@ -515,14 +529,14 @@ int fsgpu_gapless_launch(fsgpu_ctx *ctx, const int8_t *pssm, int L, int scoreCap
         if (rc != FSGPU_OK) return rc;
     } else {
         // query row tiles of 16 R <= 512 rows: tile t+1 continues every diagonal of tile t through the border arrays in HBM
-        if (R < 17 || R > kGaplessMaxR) { ctx->err = "internal: bad tiled R"; return FSGPU_E_ARG; }
+        if (R < kGaplessTiledMinR || R > kGaplessMaxR) { ctx->err = "internal: bad tiled R"; return FSGPU_E_ARG; }
         for (int t = 0; t < nTiles; t++) {
             HIPCHK(hipMemsetAsync(ctx->queue, 0, 4, ctx->stream));
             ga.tileBase = t * 16 * R;
             ga.firstTile = t == 0; ga.lastTile = t == nTiles - 1;
             ga.borderIn = (const uint16_t *) ((t & 1) ? ctx->gBorder1.p : ctx->gBorder0.p);
             ga.borderOut = (uint16_t *) ((t & 1) ? ctx->gBorder0.p : ctx->gBorder1.p);
-            if ((rc = kGaplessTiled[R - 17](ctx, ga)) != FSGPU_OK) return rc;
+            if ((rc = kGaplessTiled[R - kGaplessTiledMinR](ctx, ga)) != FSGPU_OK) return rc;
         }
     }
     HIPCHK(hipEventRecord(ctx->ev[1], ctx->stream));
@@ -581,7 +595,11 @@ int fsgpu_gapless_scan_multi(fsgpu_ctx *ctx, const fsgpu_gapless_query *q, int n
     MqBatch b;
     b.q = q; b.minScore = minScore; b.maxRes = maxRes;
     std::vector<int> longQ;
-    for (int i = 0; i < nq; i++) (q[i].L <= 16 * kGaplessMaxRUntiled ? b.batch : longQ).push_back(i);
+    for (int i = 0; i < nq; i++) {
+        int nTiles, R;
+        gaplessShape(q[i].L, &nTiles, &R);
+        (nTiles == 1 ? b.batch : longQ).push_back(i);
+    }
     std::stable_sort(b.batch.begin(), b.batch.end(), [&](int x, int y) { return (q[x].L + 15) / 16 > (q[y].L + 15) / 16; });   // long queries first
     b.nb = (int) b.batch.size();
     b.n = (uint32_t) ctx->db->n;

@@ -193,6 +193,10 @@ int64_t fsgpu_gapless_item_records(const uint64_t *items, uint64_t nItems, const
  * member out of another such class or beside a single member (that class's launch then is one record of this kind), chosen so that the
  * fewest records run without a B.  Every class present keeps exactly one launch.  Returns the number of records, or -1 for a bad argument. */
 int fsgpu_gapless_pair_halves(const int32_t *classes, int n, int32_t *launchClass, int32_t *record, int32_t *half);
+/* Host-only: the shape the scan gives a query of L residues.  *nTiles = 1 and *R = ceil(L / 16) = 1..56 registers for L <= 896 (one piece); beyond
+ * that *nTiles = ceil(L / 512) row tiles of equal height, 16 * *R rows each, *R = ceil(ceil(L / *nTiles) / 16) = 22..32.  The register class *R
+ * (with the pairing of fsgpu_gapless_scan_multi) names the kernel that runs.  Returns 0, or -1 for L outside 1 .. FSGPU_MAX_SEQ_LEN or a null pointer. */
+int fsgpu_gapless_shape(int L, int *nTiles, int *R);
 int fsgpu_gapless_launch(fsgpu_ctx *ctx, const int8_t *pssm, int L, int scoreCap, int minScore,
                          int64_t identityId, int maxRes);
 int fsgpu_gapless_finish(fsgpu_ctx *ctx, fsgpu_hit *out, int *nout);

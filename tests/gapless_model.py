@@ -1,6 +1,7 @@
 """Independent model of the gapless prefilter scan and of its top-K selection, written from the definitions alone (include/fsgpu.h,
 fsgpu_gapless_scan): plain numpy / Python ints, no call into foldseek_amd.  tests/test_gapless_model.py holds it to the C oracle, to the compiled
-reference where that is built and to a second brute-force form; tests/test_gapless_multi_gpu.py holds k_gapless and k_select to it.
+reference where that is built and to a second brute-force form; tests/test_gapless_multi_gpu.py holds k_gapless and k_select to it, and
+tests/test_gapless_sweep_gpu.py every instantiation of k_gapless (best_cells states the conditions on that sweep's inputs).
 
 A profile is the int8 [21][L] array fsgpu_gapless_scan takes (pssm[code][row]); a database is PaddedDB-like (data3di, offsets, lengths): codes
 0..20, 32 and above = soft-masked, which the scan reads as X (20)."""
@@ -79,6 +80,40 @@ def scores_brute(pssm, cap, targets):
                 best = max(best, H[i][j])
         out.append(min(clamp(cap), best))
     return np.array(out, np.int32)
+
+
+def best_cells(pssms, targets):
+    """Where the best run of each (profile, target) pair ends, by brute force over the whole matrix: pssms [n][21][L] against n code sequences, pair k =
+    (pssms[k], targets[k]).  Per pair (score, cells, start): the uncapped maximum, every (row, column) that holds it, and the cell the run into the
+    first of them starts in (back along the diagonal while the cell before it is positive).  The conditions on test inputs are stated with this."""
+    pssms = np.asarray(pssms).astype(np.int32)
+    n, _, L = pssms.shape
+    ext = np.concatenate([pssms, np.full((n, 1, L), _NEG, np.int32)], axis=1)
+    T = max(len(t) for t in targets)
+    codes = np.full((n, T), _DEAD, np.int64)
+    for k, t in enumerate(targets):
+        t = np.asarray(t).astype(np.int64)
+        codes[k, :len(t)] = np.where(t >= 32, X, t)
+    H = np.zeros((n, L, T), np.int32)
+    prev = np.zeros((n, L), np.int32)
+    pick = np.arange(n)
+    for j in range(T):
+        cur = ext[pick, codes[:, j], :].copy()
+        cur[:, 1:] += prev[:, :-1]
+        np.maximum(cur, 0, out=cur)
+        H[:, :, j] = prev = cur
+    out = []
+    for k in range(n):
+        score = int(H[k].max())
+        cells = [(int(i), int(j)) for i, j in np.argwhere(H[k] == score)] if score > 0 else []
+        start = None
+        if cells:
+            i, j = cells[0]
+            while i > 0 and j > 0 and H[k, i - 1, j - 1] > 0:
+                i, j = i - 1, j - 1
+            start = (i, j)
+        out.append((score, cells, start))
+    return out
 
 
 def select(scores, min_score, identity, max_res):
