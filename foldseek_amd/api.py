@@ -165,6 +165,8 @@ def lib():
         "fsgpu_history_counters": (None, [vp, vp]),
         "fsgpu_sw_last_passes": (None, [vp, vp]),
         "fsgpu_sw3_last_plan": (None, [vp, vp]),
+        "fsgpu_sw_kernel_counts": (None, [vp, vp]),
+        "fsgpu_sw_shape": (i32, [i32, C.POINTER(i32), C.POINTER(i32)]),
         "fsgpu_kmer_index_build": (i32, [vp, vp, vp]),
         "fsgpu_kmer_index_entries": (u64, [vp]),
         "fsgpu_kmer_index_entry_bytes": (i32, [vp]),
@@ -256,7 +258,7 @@ def exported_symbols():
             "fsgpu_db_broadcast", "fsgpu_rccl_selfcheck", "fsgpu_device_count", "fsgpu_live_devices", "fsgpu_gapless_plan_items", "fsgpu_gapless_item_records", "fsgpu_gapless_pair_halves", "fsgpu_gapless_shape", "fsgpu_block_backtrace", "fsgpu_block_backtrace_footprint",
             "fsgpu_lddt_batch", "fsgpu_tm_batch", "fsgpu_tm_superpose_batch", "fsgpu_last_kernel_ms", "fsgpu_history_counters", "fsgpu_sw_last_passes", "fsgpu_sw3_last_plan", "fsgpu_kmer_index_build", "fsgpu_kmer_index_entries", "fsgpu_kmer_index_entry_bytes", "fsgpu_kmer_index_get_params", "fsgpu_kmer_search",
             "fsgpu_kmer_index_copy", "fsgpu_kmer_row_copy", "fsgpu_kmer_last_counts", "fsgpu_kmer_last_segments", "fsgpu_kmer_plan_coarse", "fsgpu_kmer_batch_hint",
-            "fsgpu_diag_rescore", "fsgpu_sw_batch_seqs", "fsgpu_sw_scan_c", "fsgpu_sw_scan_last"]
+            "fsgpu_diag_rescore", "fsgpu_sw_batch_seqs", "fsgpu_sw_scan_c", "fsgpu_sw_scan_last", "fsgpu_sw_shape", "fsgpu_sw_kernel_counts"]
 
 
 def _ptr(a):
@@ -277,6 +279,17 @@ def gapless_shape(L):
     n_tiles, R = C.c_int(0), C.c_int(0)
     if lib().fsgpu_gapless_shape(int(L), C.byref(n_tiles), C.byref(R)) != 0:
         raise FsgpuError(f"fsgpu_gapless_shape: no query of {L} residues")
+    return n_tiles.value, R.value
+
+
+SW_R_CLASSES = (1, 2, 3, 4, 6, 8)
+
+
+def sw_shape(L):
+    """fsgpu_sw_shape (host only): (row tiles, register rows per lane R) of a query of L residues in the profile path (k_sw / k_sw2)"""
+    n_tiles, R = C.c_int(0), C.c_int(0)
+    if lib().fsgpu_sw_shape(int(L), C.byref(n_tiles), C.byref(R)) != 0:
+        raise FsgpuError(f"fsgpu_sw_shape: no query of {L} residues")
     return n_tiles.value, R.value
 
 
@@ -602,6 +615,34 @@ class Context:
         for k in keep[:nq]:
             res.append(out[b:b + len(k[1])].copy()); b += len(k[1])
         return res
+
+    def sw_multi(self, queries, gap_open=10, gap_extend=1):
+        """both directions of every pair (fsgpu_sw_multi); queries as for sw_multi_dir.  Returns (fwd, rev), one SWRES array per query each."""
+        class Q(C.Structure):
+            _fields_ = [("pAA_fwd", C.c_void_p), ("p3Di_fwd", C.c_void_p), ("pAA_rev", C.c_void_p), ("p3Di_rev", C.c_void_p),
+                        ("L", C.c_int32), ("n", C.c_int32), ("targetIds", C.c_void_p)]
+        nq = len(queries)
+        keep, arr = [], (Q * nq)()
+        for i, (paf, p3f, par_, p3r, L, ids) in enumerate(queries):
+            bufs = [None if x is None else np.ascontiguousarray(x, np.int16) for x in (paf, p3f, par_, p3r)]
+            ids = np.ascontiguousarray(ids, np.uint32)
+            keep.append((bufs, ids))
+            arr[i].pAA_fwd, arr[i].p3Di_fwd, arr[i].pAA_rev, arr[i].p3Di_rev = [None if b is None else b.ctypes.data for b in bufs]
+            arr[i].L, arr[i].n, arr[i].targetIds = int(L), len(ids), ids.ctypes.data
+        total = sum(len(k[1]) for k in keep)
+        fwd, rev = np.zeros(max(1, total), SWRES_DT), np.zeros(max(1, total), SWRES_DT)
+        self._chk(lib().fsgpu_sw_multi(self.h, C.cast(arr, C.c_void_p), nq, gap_open, gap_extend, fwd.ctypes.data, rev.ctypes.data), "fsgpu_sw_multi")
+        f, r, b = [], [], 0
+        for k in keep:
+            f.append(fwd[b:b + len(k[1])].copy()); r.append(rev[b:b + len(k[1])].copy()); b += len(k[1])
+        return f, r
+
+    def sw_kernel_counts(self):
+        """launches of every k_sw / k_sw2 instantiation by this context since it was created (fsgpu_sw_kernel_counts):
+        {(kind, has_aa, R): n}, kind 0 k_sw int16 halves, 1 k_sw int32, 2 k_sw2"""
+        o = np.zeros(36, np.uint64)
+        lib().fsgpu_sw_kernel_counts(self.h, _ptr(o))
+        return {(kind, bool(aa), R): int(o[(kind * 2 + aa) * 6 + c]) for kind in range(3) for aa in (0, 1) for c, R in enumerate(SW_R_CLASSES)}
 
     def sw_multi_dir_c(self, mat3di, matAA, queries, direction, selections=None, gap_open=10, gap_extend=1):
         """Compact form (fsgpu_sw_multi_dir_c): mat3di / matAA int8 [21, 21] (matAA None = 3Di only); queries: list of

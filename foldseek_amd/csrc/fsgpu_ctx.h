@@ -125,6 +125,7 @@ struct fsgpu_ctx {
     hipStream_t swAux[kSwAux] = {};             // created by swFork: of swHiPrio when the context has swHi, plain otherwise
     hipEvent_t swAuxEv[kSwAux + 1] = {};        // [kSwAux]: the fork event
     DevBuf img, tids, res0, res1, border0, border1, keys;
+    uint64_t swKernelCount[36] = {};            // launches per instantiation of k_sw / k_sw2 since the context was created (fsgpu_sw_kernel_counts); nothing reads them for a launch
     // per-pass accounting of the last fsgpu_sw_multi_dir calls (fsgpu_sw_last_passes): k_sw2 launches only (single-tile queries),
     // events on the context stream around the launches of one direction (the side streams of the register classes join it)
     hipEvent_t swDirEv[4] = {nullptr, nullptr, nullptr, nullptr};   // fwd start / stop, rev start / stop

@@ -17,6 +17,24 @@ static int swPickR(int rows) {
     return 8;
 }
 
+// The shape of a query of L rows: one tile of R = 1, 2, 3, 4, 6 or 8 register rows per lane (the smallest with 64 R >= L) up to 64 * kSwMaxR rows,
+// beyond that ceil(L / 512) row tiles of R = kSwMaxR.  Pure host function, exported as fsgpu_sw_shape for the CPU tests.
+static void swShape(int L, int *nTiles, int *R) {
+    *nTiles = L <= 64 * kSwMaxR ? 1 : (L + 64 * kSwMaxR - 1) / (64 * kSwMaxR);
+    *R = *nTiles == 1 ? swPickR(L) : kSwMaxR;
+}
+
+extern "C" int fsgpu_sw_shape(int L, int *nTiles, int *R) {
+    if (L < 1 || L > FSGPU_MAX_SEQ_LEN || !nTiles || !R) return -1;
+    swShape(L, nTiles, R);
+    return 0;
+}
+
+// slot of fsgpu_sw_kernel_counts: kind 0 k_sw Pk16, 1 k_sw I32, 2 k_sw2
+static constexpr int swCountSlot(int kind, bool hasAA, int R) {
+    return (kind * 2 + (hasAA ? 1 : 0)) * 6 + (R <= 4 ? R - 1 : R == 6 ? 4 : 5);
+}
+
 template <int R, bool HAS_AA, typename A>
 static int launchSwT(fsgpu_ctx *ctx, const SwArgs &sa, int blocks, int threads, hipStream_t stream) {
     const int lds = (HAS_AA ? 2 : 1) * kAlphabet * swRowDwords(R) * 4;
@@ -28,6 +46,7 @@ static int launchSwT(fsgpu_ctx *ctx, const SwArgs &sa, int blocks, int threads, 
     }
     hipLaunchKernelGGL((k_sw<R, HAS_AA, A>), dim3(blocks), dim3(threads), lds, stream, sa);
     HIPCHK(hipGetLastError());
+    ctx->swKernelCount[swCountSlot(A::packed ? 0 : 1, HAS_AA, R)]++;
     return FSGPU_OK;
 }
 
@@ -57,6 +76,7 @@ static int launchSwBlocks2T(fsgpu_ctx *ctx, const SwArgs &sa, int nBlocks, int p
     }
     hipLaunchKernelGGL((k_sw2<R, HAS_AA>), dim3(nBlocks), dim3(32 * pairsPerBlock), lds, stream, sa);
     HIPCHK(hipGetLastError());
+    ctx->swKernelCount[swCountSlot(2, HAS_AA, R)]++;
     return FSGPU_OK;
 }
 // Pairs of one query that share a workgroup (and one copy of the query's LDS image): two per wave.  8 pairs = 4 waves per image gives
@@ -96,8 +116,8 @@ static void swFillTable(uint32_t *dst, int R, int L, int base, bool packed, cons
 static int runSwPass(fsgpu_ctx *ctx, bool packed, const int16_t *pAA0, const int16_t *p3_0, const int16_t *pAA1, const int16_t *p3_1,
                      int L, const uint32_t *dTids, int nPairs, int maxLt, int go, int ge, int32_t *dRes0, int32_t *dRes1) {
     const bool hasAA = pAA0 != nullptr;
-    const int nTiles = L <= 64 * kSwMaxR ? 1 : (L + 64 * kSwMaxR - 1) / (64 * kSwMaxR);
-    const int R = nTiles == 1 ? swPickR(L) : kSwMaxR;
+    int nTiles, R;
+    swShape(L, &nTiles, &R);
     const int rowDw = swRowDwords(R);
     const size_t tblDw = (size_t) kAlphabet * rowDw;
     const size_t imgDw = tblDw * (hasAA ? 2 : 1);
@@ -196,7 +216,7 @@ static int swLongEnqueue(fsgpu_ctx *ctx, const fsgpu_sw_query *q, int nq, const 
     ctx->swLongLaunched = (uint32_t) plan.n;
     if (plan.n == 0) return FSGPU_OK;
     const size_t n = plan.n;
-    const int R = kSwMaxR, rowsPerTile = 64 * R, rowDw = swRowDwords(R);
+    const int R = kSwMaxR, rowsPerTile = 64 * R, rowDw = swRowDwords(R);       // what swShape gives every query of more than one tile
     const size_t tblDw = (size_t) kAlphabet * rowDw, imgDw = tblDw * (hasAA ? 2 : 1);
     // geometry: tiles per query, image offsets, blocks per level
     int maxTiles = 0;
@@ -205,7 +225,9 @@ static int swLongEnqueue(fsgpu_ctx *ctx, const fsgpu_sw_query *q, int nq, const 
     size_t imgTotalDw = 0;
     for (int i = 0; i < nq; i++) {
         if (qFirst[i + 1] == qFirst[i]) continue;
-        nTiles[i] = (q[i].L + rowsPerTile - 1) / rowsPerTile;
+        int tileR;
+        swShape(q[i].L, &nTiles[i], &tileR);
+        if (tileR != R || nTiles[i] < 2) { ctx->err = "internal: a single-tile query among the row-tiled ones"; return FSGPU_E_ARG; }
         maxTiles = std::max(maxTiles, nTiles[i]);
         imgFirst[i] = imgTotalDw;
         imgTotalDw += imgDw * (size_t) nTiles[i];
@@ -465,7 +487,11 @@ int fsgpu_sw_multi_dir(fsgpu_ctx *ctx, const fsgpu_sw_query *q, int nq, int gapO
     {
         std::vector<char> isLong(nq, 0);
         bool any = false;
-        for (int i = 0; i < nq; i++) if (q[i].L > 64 * kSwMaxR && nSel(i) > 0) { isLong[i] = 1; any = true; }
+        for (int i = 0; i < nq; i++) {
+            int tiles, R;
+            swShape(q[i].L, &tiles, &R);
+            if (tiles > 1 && nSel(i) > 0) { isLong[i] = 1; any = true; }
+        }
         if (any && (rc = swLongEnqueue(ctx, q, nq, isLong, sel, nsel, base, hasAA, gapOpen, gapExtend, dir, out, longPlan)) != FSGPU_OK) {
             if (ctx->swLong) (void) hipStreamSynchronize(ctx->swLong);
             return rc;
@@ -478,7 +504,11 @@ int fsgpu_sw_multi_dir(fsgpu_ctx *ctx, const fsgpu_sw_query *q, int nq, int gapO
     // ---- launch groups by register class ----
     const int classes[6] = {1, 2, 3, 4, 6, 8};
     std::vector<int> cls(nq, -1);
-    for (int i = 0; i < nq; i++) if (q[i].L <= 64 * kSwMaxR && nSel(i) > 0) cls[i] = swPickR(q[i].L);
+    for (int i = 0; i < nq; i++) {
+        int tiles, R;
+        swShape(q[i].L, &tiles, &R);
+        if (tiles == 1 && nSel(i) > 0) cls[i] = R;
+    }
     size_t imgDwTotal = 0, nBlocks = 0;
     const int ppb = sw2PairsPerBlock();
     for (int i = 0; i < nq; i++) if (cls[i] > 0) { imgDwTotal += (size_t) kSw2Rows * swRowDwords(cls[i]) * (hasAA ? 2 : 1); nBlocks += ((size_t) nSel(i) + ppb - 1) / ppb; }
@@ -633,6 +663,10 @@ int fsgpu_sw_multi(fsgpu_ctx *ctx, const fsgpu_sw_query *q, int nq, int gapOpen,
     int rc = fsgpu_sw_multi_dir(ctx, q, nq, gapOpen, gapExtend, 0, nullptr, nullptr, fwd);
     if (rc != FSGPU_OK) return rc;
     return fsgpu_sw_multi_dir(ctx, q, nq, gapOpen, gapExtend, 1, nullptr, nullptr, rev);
+}
+
+void fsgpu_sw_kernel_counts(const fsgpu_ctx *ctx, uint64_t out[36]) {
+    for (int i = 0; i < 36; i++) out[i] = ctx ? ctx->swKernelCount[i] : 0;
 }
 
 } // extern "C"

@@ -15,7 +15,7 @@
 // row above, both F chains, and the target residue itself -- rides a one-lane-per-step conveyor built from
 // v_mov_b32_dpp wave_shr:1.  The forward-query and reversed-query passes of structurealign (structurealign.cpp:46,65)
 // share the target and the control flow, so they are packed into the two int16 halves of every register:
-// v_pk_add_i16 clamp reproduces _mm256_adds_epi16, v_pk_sub_u16 clamp reproduces _mm256_subs_epu16.
+// v_pk_add_i16 clamp reproduces _mm256_adds_epi16 (H + s, and the AA + 3Di sum of the column score), v_pk_sub_u16 clamp reproduces _mm256_subs_epu16.
 // Pairs whose int16 score saturates (32767) are re-run by the int32 instantiation with segLen = ceil(L/8), as
 // alignScoreEndPos does (:313-336).  Queries longer than 64*R rows are processed in row tiles; the three
 // boundary values per target column travel between tile launches through HBM (border arrays).
@@ -34,6 +34,9 @@ struct Pk16 {                        // two independent int16 problems per regis
         return __builtin_bit_cast(uint32_t, (s16x2) (__builtin_bit_cast(s16x2, a) + __builtin_bit_cast(s16x2, b)));
     }
     static __device__ __forceinline__ uint32_t adds(uint32_t a, uint32_t b) { return pk_adds_i16(a, b); }
+    // the column score, AA entry + 3Di entry: the reference sums the two tables with simdi16_adds (StructureSmithWaterman.cpp:1178), and the
+    // entries take any int16, so the sum can leave the range; the same v_pk_add_i16 as the wrapping add, with the clamp bit
+    static __device__ __forceinline__ uint32_t psum(uint32_t a, uint32_t b) { return pk_adds_i16(a, b); }
     static __device__ __forceinline__ uint32_t max(uint32_t a, uint32_t b) { return pk_max_i16(a, b); }
     static __device__ __forceinline__ uint32_t subus(uint32_t a, uint32_t b) {
         return __builtin_bit_cast(uint32_t, __builtin_elementwise_sub_sat(__builtin_bit_cast(u16x2, a), __builtin_bit_cast(u16x2, b)));
@@ -53,6 +56,7 @@ struct I32 {                         // one int32 problem per register (re-run o
     static constexpr bool packed = false;
     static __device__ __forceinline__ uint32_t add(uint32_t a, uint32_t b) { return a + b; }
     static __device__ __forceinline__ uint32_t adds(uint32_t a, uint32_t b) { return a + b; }
+    static __device__ __forceinline__ uint32_t psum(uint32_t a, uint32_t b) { return a + b; }    // simdi32_add in the reference's int32 pass (:1410)
     static __device__ __forceinline__ uint32_t max(uint32_t a, uint32_t b) { return (uint32_t) ::max((int) a, (int) b); }
     static __device__ __forceinline__ uint32_t subus(uint32_t a, uint32_t b) { return (uint32_t) ::max((int) a - (int) b, 0); }
     static __device__ __forceinline__ uint32_t gtMask(uint32_t a, uint32_t b) { return ((int) a > (int) b) ? 0xffffffffu : 0u; }
@@ -268,7 +272,7 @@ __global__ __launch_bounds__(512) void k_sw(SwArgs a) {
 #pragma unroll
             for (int r = 0; r < R; r++) {
                 uint32_t sc = P3[r];
-                if constexpr (HAS_AA) sc = A::add(PA[r], sc);
+                if constexpr (HAS_AA) sc = A::psum(PA[r], sc);
                 uint32_t h = A::adds(diag, sc);
                 h = A::max(h, E[r]);
                 fseg &= segmask[r];
@@ -464,7 +468,7 @@ __global__ __launch_bounds__(1024) void k_sw2(SwArgs a) {
                 swLoadRow<R>(lbA, tvalAA & 0xffffu, QA);
                 swLoadRow<R>(lbA, tvalAA >> 16, QB);
 #pragma unroll
-                for (int r = 0; r < R; r++) { PA[r] = A::add(QA[r], PA[r]); PB[r] = A::add(QB[r], PB[r]); }
+                for (int r = 0; r < R; r++) { PA[r] = A::psum(QA[r], PA[r]); PB[r] = A::psum(QB[r], PB[r]); }
             }
             uint32_t diag = hUpPrev, fseg = fsegIn, ffull = ffullIn, cm = 0;
 #pragma unroll

@@ -208,7 +208,14 @@ int fsgpu_gapless_finish(fsgpu_ctx *ctx, fsgpu_hit *out, int *nout);
  * pAA_* may be NULL when the AA matrix is all zero (--alignment-type 0).
  * For every targetIds[k] the call returns alignScoreEndPos(...) of the forward profile in fwd[k] and of the
  * reversed-query profile in rev[k], bit-identical to the AVX2 striped kernels including the int16->int32 re-run.
+ * The tables may hold any int16: the column score is the SATURATING int16 sum of the AA and the 3Di entry, as the reference's
+ * simdi16_adds makes it (StructureSmithWaterman.cpp:1178), and the plain sum in the int32 re-run (:1410); what the caller has to
+ * keep is the int32 pass below 2^31 (min(L, target length) * 65534 at most: any pair of up to 32768 rows or columns).
  * Requires gapOpen > gapExtend >= 0 (Foldseek: 10/1); otherwise FSGPU_E_UNSUPPORTED. */
+/* Host-only: the shape the profile path (k_sw / k_sw2) gives a query of L residues.  *nTiles = 1 and *R = the smallest of 1, 2, 3, 4, 6, 8 register
+ * rows per lane with 64 * *R >= L for L <= 512; beyond that *nTiles = ceil(L / 512) row tiles of *R = 8.  Returns 0, or -1 for L outside
+ * 1 .. FSGPU_MAX_SEQ_LEN or a null pointer. */
+int fsgpu_sw_shape(int L, int *nTiles, int *R);
 int fsgpu_sw_batch(fsgpu_ctx *ctx, const int16_t *pAA_fwd, const int16_t *p3Di_fwd,
                    const int16_t *pAA_rev, const int16_t *p3Di_rev, int L,
                    const uint32_t *targetIds, int n, int gapOpen, int gapExtend,
@@ -570,6 +577,10 @@ void fsgpu_sw_last_passes(const fsgpu_ctx *ctx, double *out);
  * (0: those of an earlier call over the same queries were reused, or no pair ran through k_sw3); [9] launch groups per direction; [10] workgroups per direction;
  * [11] 0. */
 void fsgpu_sw3_last_plan(const fsgpu_ctx *ctx, uint32_t *out);
+/* out[36]: launches of every instantiation of the profile path's kernels by this context since it was created (a clone starts at zero; counters
+ * only, nothing reads them for a launch).  Index (kind * 2 + hasAA) * 6 + c: kind 0 k_sw with the two int16 halves, 1 k_sw in int32 (the re-run of
+ * saturated pairs), 2 k_sw2; hasAA 1 with an AA table; c the index of R in {1, 2, 3, 4, 6, 8}. */
+void fsgpu_sw_kernel_counts(const fsgpu_ctx *ctx, uint64_t out[36]);
 
 #ifdef __cplusplus
 }
