@@ -42,6 +42,12 @@ class KmerQuery(C.Structure):
                 ("reserved", C.c_int32), ("identity", C.c_int64)]
 
 
+class KmerProfileQuery(C.Structure):
+    """fsgpu_kmer_profile_query"""
+    _fields_ = [("seq", C.c_void_p), ("scores", C.c_void_p), ("profile", C.c_void_p), ("L", C.c_int32), ("kmerThr", C.c_int32),
+                ("identity", C.c_int64)]
+
+
 class GaplessQuery(C.Structure):
     """fsgpu_gapless_query"""
     _fields_ = [("pssm", C.c_void_p), ("L", C.c_int32), ("scoreCap", C.c_int32), ("identityId", C.c_int64)]
@@ -236,6 +242,13 @@ def lib():
         "fsgpu_diag_rescore": (i32, [vp, vp, vp, vp, vp, i32, vp, vp, vp, i64, vp]),
         "fshost_search_prefilter_batch": (i32, [vp, i32, vp, vp, vp, vp, vp]),
         "fshost_search_kmer_batch": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "fsgpu_kmer_search_profile": (i32, [vp, vp, vp, i32, vp, vp, vp, vp]),
+        "fsgpu_kmer_profile_list_copy": (i32, [vp, i32, i32, vp, C.c_uint32, vp]),
+        "fsgpu_kmer_profile_sort_rows": (i32, [vp, i32, vp]),
+        "fshost_profile_decode_raw": (i32, [vp, C.c_size_t, vp, vp, vp, vp, vp, C.c_char_p, C.c_size_t]),
+        "fshost_kmer_threshold_profile": (i32, [f32, i32, i32]),
+        "fshost_kmer_query_prepare_profile": (i32, [vp, C.c_size_t, i32, i32, i32, vp, vp, vp, vp, C.c_char_p, C.c_size_t]),
+        "fshost_search_kmer_batch_profile": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "fshost_search_rescore_diagonal_batch": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "fshost_banded_backtrace": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, C.POINTER(C.c_uint), C.c_char_p, C.c_size_t]),
         "fshost_search_startpos_backtrace": (i32, [vp, vp, vp, i32, C.c_uint32, i32, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(C.c_uint), C.c_char_p, C.c_size_t]),
@@ -258,6 +271,7 @@ def exported_symbols():
             "fsgpu_db_broadcast", "fsgpu_rccl_selfcheck", "fsgpu_device_count", "fsgpu_live_devices", "fsgpu_gapless_plan_items", "fsgpu_gapless_item_records", "fsgpu_gapless_pair_halves", "fsgpu_gapless_shape", "fsgpu_block_backtrace", "fsgpu_block_backtrace_footprint",
             "fsgpu_lddt_batch", "fsgpu_tm_batch", "fsgpu_tm_superpose_batch", "fsgpu_last_kernel_ms", "fsgpu_history_counters", "fsgpu_sw_last_passes", "fsgpu_sw3_last_plan", "fsgpu_kmer_index_build", "fsgpu_kmer_index_entries", "fsgpu_kmer_index_entry_bytes", "fsgpu_kmer_index_get_params", "fsgpu_kmer_search",
             "fsgpu_kmer_index_copy", "fsgpu_kmer_row_copy", "fsgpu_kmer_last_counts", "fsgpu_kmer_last_segments", "fsgpu_kmer_plan_coarse", "fsgpu_kmer_batch_hint",
+            "fsgpu_kmer_search_profile", "fsgpu_kmer_profile_list_copy", "fsgpu_kmer_profile_sort_rows",
             "fsgpu_diag_rescore", "fsgpu_sw_batch_seqs", "fsgpu_sw_scan_c", "fsgpu_sw_scan_last", "fsgpu_sw_shape", "fsgpu_sw_kernel_counts"]
 
 
@@ -554,6 +568,43 @@ class Context:
                   "fsgpu_kmer_search")
         res = [out[q, :nout[q]].copy() for q in range(nq)]
         return (res, status[:nq], stats[:nq]) if want_stats else (res, status[:nq])
+
+    def kmer_search_profile(self, prepared, identity=None, max_res=1000, min_diag=30, bins=0, max_db_matches=0, found_diagonals_size=0, l2_cache_size=0,
+                            want_stats=False, kmer_score_only=False):
+        """fsgpu_kmer_search_profile.  prepared: list of (seq uint8[L], scores int8[L,20], profile int8[L,21], kmerThr) from kmer_query_prepare_profile;
+        the resident index must have been built with kmer_thr=0."""
+        nq = len(prepared)
+        sp = KmerSearchParams(max_res, min_diag, bins, 1 if kmer_score_only else 0, max_db_matches, found_diagonals_size, l2_cache_size)
+        qs = (KmerProfileQuery * max(nq, 1))()
+        keep = []
+        for i, (seq, scores, prof, thr) in enumerate(prepared):
+            seq = np.ascontiguousarray(seq, np.uint8); scores = np.ascontiguousarray(scores, np.int8).reshape(-1, 20)
+            prof = np.ascontiguousarray(prof, np.int8).reshape(-1, 21)
+            if len(scores) != len(seq) or len(prof) != len(seq):
+                raise FsgpuError("kmer_search_profile: letters, score rows and profile differ in length")
+            keep.append((seq, scores, prof))
+            qs[i].seq = seq.ctypes.data; qs[i].scores = scores.ctypes.data; qs[i].profile = prof.ctypes.data
+            qs[i].L = len(seq); qs[i].kmerThr = int(thr)
+            qs[i].identity = -1 if identity is None else int(identity[i])
+        out = np.zeros((max(nq, 1), max_res), KMER_HIT_DT)
+        nout = np.zeros(max(nq, 1), np.int32)
+        status = np.zeros(max(nq, 1), np.int32)
+        stats = np.zeros((max(nq, 1), 4))
+        self._chk(lib().fsgpu_kmer_search_profile(self.h, C.byref(sp), C.cast(qs, C.c_void_p), nq, _ptr(out), _ptr(nout), _ptr(status), _ptr(stats)),
+                  "fsgpu_kmer_search_profile")
+        res = [out[q, :nout[q]].copy() for q in range(nq)]
+        return (res, status[:nq], stats[:nq]) if want_stats else (res, status[:nq])
+
+    def kmer_profile_list(self, query, pos, cap=None):
+        """fsgpu_kmer_profile_list_copy: (K_p, similar k-mers uint32 in emission order, reference numbering) of k-mer start `pos` of query `query` of the
+        last device batch, which must have been a profile batch"""
+        cnt = C.c_uint32(0)
+        self._chk(lib().fsgpu_kmer_profile_list_copy(self.h, int(query), int(pos), None, 0, C.byref(cnt)), "fsgpu_kmer_profile_list_copy")
+        n = cnt.value if cap is None else min(cnt.value, int(cap))
+        out = np.zeros(max(n, 1), np.uint32)
+        if n:
+            self._chk(lib().fsgpu_kmer_profile_list_copy(self.h, int(query), int(pos), _ptr(out), n, C.byref(cnt)), "fsgpu_kmer_profile_list_copy")
+        return int(cnt.value), out[:n]
 
     def kmer_counts(self):
         """last batch: similar k-mers probed, index hits, double-diagonal candidates, elements handed to the host"""
@@ -1277,6 +1328,28 @@ class Search:
             raise FsgpuError(f"kmer_batch rc={rc}: {lib().fshost_search_error(self.h).decode()}")
         return out
 
+    def kmer_batch_profile(self, entries, kmer_thr, spaced, pref_identity=None, aln_identity=None, max_res=200, min_diag=30, kmer_score_only=False):
+        """fshost_search_kmer_batch_profile: the profile form of kmer_batch.  entries: [(AA entry, 3Di entry)] of the profile databases (bytes without the
+        terminator).  Returns the same dict as kmer_batch (results [nq, max_res])."""
+        nq = len(entries)
+        bufs = [(np.frombuffer(bytes(a), np.uint8).copy(), np.frombuffer(bytes(b), np.uint8).copy()) for a, b in entries]
+        pa = np.array([a.ctypes.data for a, _ in bufs] + [0], np.uint64); p3 = np.array([b.ctypes.data for _, b in bufs] + [0], np.uint64)
+        la = np.array([len(a) for a, _ in bufs] + [0], np.uint64); l3 = np.array([len(b) for _, b in bufs] + [0], np.uint64)
+        assert C.sizeof(C.c_size_t) == 8
+        pi = None if pref_identity is None else np.ascontiguousarray(pref_identity, np.int64)
+        ai = None if aln_identity is None else np.ascontiguousarray(aln_identity, np.int64)
+        sp = KmerSearchParams(max_res, min_diag, 0, 1 if kmer_score_only else 0, 0, 0, 0)
+        n1 = max(nq, 1)
+        out = {"hits": np.zeros((n1, max_res), KMER_HIT_DT), "nhits": np.zeros(n1, np.int32), "status": np.zeros(n1, np.int32),
+               "kept": np.zeros((n1, max_res), np.uint32), "nkept": np.zeros(n1, np.int32), "results": np.zeros((n1, max_res), RESULT_DT),
+               "nres": np.zeros(n1, np.int32), "seconds": np.zeros(4)}
+        rc = lib().fshost_search_kmer_batch_profile(self.h, C.cast(C.byref(sp), C.c_void_p), int(kmer_thr), int(spaced), nq, _ptr(pa), _ptr(la), _ptr(p3), _ptr(l3),
+                                                    _ptr(pi), _ptr(ai), _ptr(out["hits"]), _ptr(out["nhits"]), _ptr(out["status"]), _ptr(out["kept"]),
+                                                    _ptr(out["nkept"]), _ptr(out["results"]), _ptr(out["nres"]), _ptr(out["seconds"]))
+        if rc != 0:
+            raise FsgpuError(f"kmer_batch_profile rc={rc}: {lib().fshost_search_error(self.h).decode()}")
+        return out
+
     def set_tm(self, tm_thr=0.0, mode=0, structure_bits=False):
         """fshost_search_set_tm: --tmscore-threshold, --tmscore-threshold-mode (0 alignment, 1 query, 2 target), --sort-by-structure-bits; call it before
         bind_ca"""
@@ -1422,6 +1495,51 @@ def profile_decode(entry):
     if L and lib().fshost_profile_decode(_ptr(buf), len(buf), _ptr(codes), _ptr(cons), _ptr(prof), _ptr(rev), err, len(err)) != L:
         raise FsgpuError(err.value.decode())
     return codes, cons, prof, rev
+
+
+def profile_decode_raw(entry):
+    """fshost_profile_decode_raw: profile_decode's four arrays and the raw score rows int8 [L, 20] the k-mer generator reads"""
+    buf = np.frombuffer(bytes(entry), np.uint8)
+    err = C.create_string_buffer(256)
+    L = lib().fshost_profile_decode_raw(_ptr(buf) if len(buf) else None, len(buf), None, None, None, None, None, err, len(err))
+    if L < 0:
+        raise FsgpuError(f"profile_decode_raw rc={L}: {err.value.decode()}")
+    codes = np.zeros(L, np.uint8); cons = np.zeros(L, np.uint8); prof = np.zeros((21, L), np.int8); rev = np.zeros((21, L), np.int8)
+    raw = np.zeros((L, 20), np.int8)
+    if L and lib().fshost_profile_decode_raw(_ptr(buf), len(buf), _ptr(codes), _ptr(cons), _ptr(prof), _ptr(rev), _ptr(raw), err, len(err)) != L:
+        raise FsgpuError("profile_decode_raw: inconsistent length")
+    return codes, cons, prof, rev, raw
+
+
+def kmer_threshold_profile(sensitivity=9.5, kmer_size=6, context_pseudo_counts=True):
+    """fshost_kmer_threshold_profile: Prefiltering::getKmerThreshold for a profile query"""
+    return lib().fshost_kmer_threshold_profile(sensitivity, kmer_size, 1 if context_pseudo_counts else 0)
+
+
+def kmer_query_prepare_profile(entry_3di, kmer_thr, kmer_size=6, spaced=1):
+    """fshost_kmer_query_prepare_profile -> (seq uint8[L], scores int8[L,20], profile int8[L,21], threshold) for Context.kmer_search_profile"""
+    buf = np.frombuffer(bytes(entry_3di), np.uint8)
+    err = C.create_string_buffer(256)
+    if len(buf) % 25:
+        raise FsgpuError("kmer_query_prepare_profile: the entry is no multiple of the record size")
+    L = len(buf) // 25
+    codes = np.zeros(L, np.uint8); raw = np.zeros((L, 20), np.int8); prof = np.zeros((L, 21), np.int8)
+    thr = C.c_int32(0)
+    n = lib().fshost_kmer_query_prepare_profile(_ptr(buf) if L else None, len(buf), int(kmer_thr), int(kmer_size), int(spaced), _ptr(codes), _ptr(raw), _ptr(prof),
+                                                C.cast(C.byref(thr), C.c_void_p), err, len(err))
+    if n < 0:
+        raise FsgpuError(f"kmer_query_prepare_profile rc={n}: {err.value.decode()}")
+    return codes, raw, prof, int(thr.value)
+
+
+def kmer_profile_sort_rows(scores):
+    """fsgpu_kmer_profile_sort_rows (host only): int8 [L, 20] -> (sorted scores int16 [L, 20], letters uint8 [L, 20]) as the device reads the rows"""
+    sc = np.ascontiguousarray(scores, np.int8).reshape(-1, 20)
+    rows = np.zeros((len(sc), 20), np.uint16)
+    rc = lib().fsgpu_kmer_profile_sort_rows(_ptr(sc), len(sc), _ptr(rows))
+    if rc != 0:
+        raise FsgpuError(f"fsgpu_kmer_profile_sort_rows rc={rc}")
+    return (rows.view(np.int16) >> 8).astype(np.int16), (rows & 0xff).astype(np.uint8)
 
 
 def profile_bias(profile):

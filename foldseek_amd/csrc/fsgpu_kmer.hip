@@ -16,6 +16,7 @@
 
 #include "fsgpu_ctx.h"
 #include "k_kmer.hpp"
+#include "k_kmer_profile.hpp"
 
 #include <functional>
 void fshostParallelFor(int n, const std::function<void(int)> &fn);      // host/search.cpp: the library's host worker pool
@@ -114,6 +115,9 @@ struct KmerScratch {
     KPin<KmerQ> hQs; KPin<KmerChunks> hChunks; KPin<KmerOut> hOut; KPin<uint8_t> hSeqs, hTiles; KPin<int8_t> hProfiles; KPin<uint16_t> hPosQuery; KPin<int16_t> hThrs;
     KPin<uint32_t> hEc, hRounds, hThr, hOutCount; KPin<unsigned long long> hResSize;
     KPin<uint64_t> hMisc;                 // 32 words: [0] lists, [1] hits, [2] candidates of the batch
+    // profile queries (fsgpu_kmer_search_profile): the sorted score rows of every query position, score << 8 | letter, and where a query's rows start
+    KDev<uint16_t> rows; KDev<uint64_t> rowBase; KPin<uint16_t> hRows; KPin<uint64_t> hRowBase;
+    int profNq = 0; uint64_t profNPos = 0, profNLists = 0;          // the last device batch when it was a profile batch (fsgpu_kmer_profile_list_copy), else 0
     hipEvent_t ev[14] = {};
     bool evInit = false;
     const uint32_t *candTotal() const { return nCand.p; }
@@ -613,6 +617,7 @@ static KmerSwitches readSwitches() {
 struct KmerBatch {
     fsgpu_ctx *ctx; KmerScratch &S; const KmerIndex &ix; const fsgpu_kmer_search_params &sp; const fsgpu_kmer_query *queries; int nq; hipStream_t st;
     KmerSwitches sw;
+    const fsgpu_kmer_profile_query *pq = nullptr;    // profile form: the same nq queries with their raw score rows (queries[] then carries letters, profile, identity)
     uint64_t nPos = 0, nLists = 0, nHits = 0;
     uint32_t nCand = 0, maxChunks = 1;               // maxChunks: the most chunks (databaseHits refills + 1) a query of the batch has
     const KmerChunks *hck = nullptr;                 // the chunk tables on the host (S.hChunks): from kmerSimilar on
@@ -640,16 +645,26 @@ constexpr int kKmerHalve = 1;
 static int kmerStageQueries(KmerBatch &B) {
     fsgpu_ctx *ctx = B.ctx; KmerScratch &S = B.S; const KmerIndex &ix = B.ix; const hipStream_t st = B.st; const int nq = B.nq;
     const fsgpu_kmer_query *queries = B.queries;
-    uint64_t &nPos = B.nPos, seqBytes = 0, profBytes = 0;
+    uint64_t &nPos = B.nPos, seqBytes = 0, profBytes = 0, nRows = 0;
     for (int q = 0; q < nq; q++) {
         const int L = queries[q].L;
         if (L < 0 || L > FSGPU_MAX_SEQ_LEN || (L > 0 && (!queries[q].seq || !queries[q].profile))) { ctx->err = "k-mer search: bad query"; return FSGPU_E_ARG; }
         if (L >= 32768) { ctx->err = "k-mer search: queries of 32768 residues or more are not supported on the device"; return FSGPU_E_UNSUPPORTED; }
+        if (B.pq && L > 0 && !B.pq[q].scores) { ctx->err = "k-mer search: profile query without score rows"; return FSGPU_E_ARG; }
         nPos += (uint64_t) std::max(0, L - ix.pat.size + 1);
         seqBytes += (uint64_t) L + 16;
         profBytes += (uint64_t) L * 21 + 16;
+        nRows += (uint64_t) L;
     }
+    S.profNq = 0; S.profNPos = S.profNLists = 0;
     KCHK(ensureAllK(ctx, S.hQs, nq, S.hPosQuery, nPos + 1, S.hSeqs, seqBytes, S.hThrs, nPos + 1, S.hProfiles, profBytes));
+    if (B.pq) {
+        // the rows are sorted here, once per query position, the way Sequence::mapProfile leaves them (Util::rankedDescSort20): the kernels read them as they are
+        KCHK(ensureAllK(ctx, S.hRows, nRows * 20 + 1, S.hRowBase, nq, S.rows, nRows * 20 + 1, S.rowBase, nq));
+        uint64_t ro = 0;
+        for (int q = 0; q < nq; q++) { S.hRowBase.p[q] = ro; ro += (uint64_t) queries[q].L; }
+        fshostParallelFor(nq, [&](int q) { if (queries[q].L > 0) fsgpu_kmer_profile_sort_rows(B.pq[q].scores, queries[q].L, S.hRows.p + S.hRowBase.p[q] * 20); });
+    }
     KmerQ *hq = S.hQs.p;
     uint64_t pb = 0, so = 0, po = 0;
     for (int q = 0; q < nq; q++) {
@@ -661,7 +676,12 @@ static int kmerStageQueries(KmerBatch &B) {
         for (int i = 0; i < L; i++) { uint8_t c = queries[q].seq[i]; c = c >= 32 ? c - 32 : c; sd[i] = c > 20 ? 20 : c; }
         memset(sd + L, 20, 16);
         if (L) memcpy(S.hProfiles.p + po, queries[q].profile, (size_t) L * 21);
-        for (uint32_t i = 0; i < np; i++) { S.hPosQuery.p[pb + i] = (uint16_t) q; S.hThrs.p[pb + i] = queries[q].kmerThr ? queries[q].kmerThr[i] : (int16_t) ix.p.kmerThr; }
+        // a profile query has no composition bias (QueryMatcher.cpp:109-117): every position's threshold is max(kmerThr, 0) (:271)
+        const int16_t pthr = B.pq ? (int16_t) std::min(std::max(B.pq[q].kmerThr, 0), 32767) : 0;
+        for (uint32_t i = 0; i < np; i++) {
+            S.hPosQuery.p[pb + i] = (uint16_t) q;
+            S.hThrs.p[pb + i] = B.pq ? pthr : queries[q].kmerThr ? queries[q].kmerThr[i] : (int16_t) ix.p.kmerThr;
+        }
         pb += np; so += (uint64_t) L + 16; po += (uint64_t) L * 21 + 16;
     }
     const size_t perChunk = (size_t) nq * kMaxChunks;
@@ -675,6 +695,10 @@ static int kmerStageQueries(KmerBatch &B) {
     HIPCHK(kCopy(S.seqs.p, S.hSeqs.p, seqBytes, hipMemcpyHostToDevice, st));
     HIPCHK(kCopy(S.thrs.p, S.hThrs.p, nPos + 1, hipMemcpyHostToDevice, st));
     HIPCHK(kCopy(S.profiles.p, S.hProfiles.p, profBytes, hipMemcpyHostToDevice, st));
+    if (B.pq) {
+        if (nRows) HIPCHK(kCopy(S.rows.p, S.hRows.p, nRows * 20, hipMemcpyHostToDevice, st));
+        HIPCHK(kCopy(S.rowBase.p, S.hRowBase.p, nq, hipMemcpyHostToDevice, st));
+    }
     HIPCHK(kZero(S.ec.p, perChunk, st));
     HIPCHK(kZero(S.rounds.p, perChunk, st));
     HIPCHK(kZero(S.resSize.p, nq, st));
@@ -691,7 +715,13 @@ static int kmerSimilar(KmerBatch &B) {
     fsgpu_ctx *ctx = B.ctx; KmerScratch &S = B.S; const KmerIndex &ix = B.ix; const hipStream_t st = B.st; const int nq = B.nq;
     const uint64_t nPos = B.nPos, maxDbMatches = B.sp.maxDbMatches ? (uint64_t) B.sp.maxDbMatches : std::max<uint64_t>(ix.n, 1000000) * 2;
     ctx->kmerForm[0] = ctx->kmerForm[1] = 0;
-    if (nPos) {
+    if (nPos && B.pq) {
+        // profile form: one workgroup per position builds the count tables of its six rows (k_kmer_profile.hpp)
+        ctx->kmerForm[0] = 1;
+        hipLaunchKernelGGL(k_kmer_count_p, dim3((unsigned) nPos), dim3(kKmerBlock), 0, st, S.qs.p, S.posQuery.p, S.seqs.p, S.thrs.p, S.rows.p, S.rowBase.p, (uint32_t) nPos,
+                           ix.pat, S.K.p);
+        HIPCHK(hipGetLastError());
+    } else if (nPos) {
         const bool w = B.sw.wave >= 0 ? B.sw.wave != 0 : (ctx->kmerKPerPos > 0 && ctx->kmerKPerPos < 2048);
         ctx->kmerForm[0] = w ? 2 : 1;
         auto count = [&](auto kernel, unsigned grid, unsigned block) {
@@ -713,7 +743,14 @@ static int kmerSimilar(KmerBatch &B) {
     }
     HIPCHK(hipEventRecord(S.ev[1], st));
     KCHK(ensureAllK(ctx, S.listStart, nLists + 1, S.listSize, nLists + 1, S.listPos, nLists + 1, S.listP, nLists + 1));
-    if (nLists) {
+    if (nLists && B.pq) {
+        HIPCHK(hipEventRecord(S.ev[10], st));
+        ctx->kmerForm[1] = 1;
+        hipLaunchKernelGGL(k_kmer_lists_p<false>, dim3((unsigned) (nPos + nLists / kListSlice + 1)), dim3(kKmerBlock), 0, st, S.qs.p, S.posQuery.p, S.seqs.p, S.thrs.p, S.rows.p,
+                           S.rowBase.p, (uint32_t) nPos, ix.pat, S.K.p, S.Kbase.p, ix.offsets, ix.bitmap, S.listStart.p, S.listSize.p, S.listPos.p, 0u, (uint32_t *) nullptr);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(S.ev[11], st));
+    } else if (nLists) {
         HIPCHK(hipEventRecord(S.ev[10], st));
         ctx->kmerKPerPos = (double) nLists / (double) std::max<uint64_t>(nPos, 1);
         ctx->kmerForm[1] = (B.sw.wave >= 0 ? B.sw.wave != 0 : ctx->kmerKPerPos < 2048) ? 2 : 1;
@@ -745,6 +782,7 @@ static int kmerSimilar(KmerBatch &B) {
     HIPCHK(kCopy(S.hQs.p, S.qs.p, nq, hipMemcpyDeviceToHost, st));
     KCHK(syncStream(ctx));
     B.hck = S.hChunks.p;
+    if (B.pq) { S.profNq = nq; S.profNPos = nPos; S.profNLists = nLists; }
     for (int q = 0; q < nq; q++) B.maxChunks = std::max<uint32_t>(B.maxChunks, B.hck[q].nChunks);
     if (compactChunks && B.maxChunks > 8) {
         const size_t upTo = offsetof(KmerChunks, start) + ((size_t) std::min<uint32_t>(B.maxChunks, kMaxChunks) + 1) * sizeof(uint64_t);
@@ -1054,14 +1092,14 @@ static void kmerHostTail(KmerBatch &B, fsgpu_kmer_hit *out, int32_t *nout, int32
     B.mark("host tail");
 }
 
-static int kmerBatch(fsgpu_ctx *ctx, const fsgpu_kmer_search_params &sp, const fsgpu_kmer_query *queries, int nq,
+static int kmerBatch(fsgpu_ctx *ctx, const fsgpu_kmer_search_params &sp, const fsgpu_kmer_query *queries, const fsgpu_kmer_profile_query *pq, int nq,
                      fsgpu_kmer_hit *out, int32_t *nout, int32_t *status, double *stats) {
     if (!ctx->kmer) ctx->kmer = new KmerScratch();
     KmerScratch &S = *ctx->kmer;
     if (!S.evInit) { for (hipEvent_t &e : S.ev) HIPCHK(hipEventCreate(&e)); S.evInit = true; }
     static const bool trace = getenv("FSGPU_KMER_TRACE") != nullptr;
     KmerBatch B{ctx, S, *ctx->kidx, sp, queries, nq, ctx->stream, readSwitches()};
-    B.trace = trace; B.tPrev = std::chrono::steady_clock::now();
+    B.trace = trace; B.tPrev = std::chrono::steady_clock::now(); B.pq = pq;
     const hipStream_t st = B.st;
     KCHK(kmerStageQueries(B));
     KCHK(kmerSimilar(B));
@@ -1089,10 +1127,9 @@ static int kmerBatch(fsgpu_ctx *ctx, const fsgpu_kmer_search_params &sp, const f
     return FSGPU_OK;
 }
 
-extern "C" int fsgpu_kmer_search(fsgpu_ctx *ctx, const fsgpu_kmer_search_params *p, const fsgpu_kmer_query *queries, int nq,
-                                 fsgpu_kmer_hit *out, int32_t *nout, int32_t *status, double *stats) {
-    if (!ctx || !p || (nq > 0 && (!queries || !out || !nout || !status))) return FSGPU_E_ARG;
-    if (!ctx->kidx) { ctx->err = "k-mer index not built"; return FSGPU_E_NODB; }
+// both forms of the search: pq == nullptr for sequence queries; for profile queries queries[] carries letters, ungapped profile and identity
+static int kmerSearch(fsgpu_ctx *ctx, const fsgpu_kmer_search_params *p, const fsgpu_kmer_query *queries, const fsgpu_kmer_profile_query *pq, int nq,
+                      fsgpu_kmer_hit *out, int32_t *nout, int32_t *status, double *stats) {
     if (p->maxResListLen <= 0 || p->minDiagScoreThr < 0 || p->minDiagScoreThr > 255 * (p->kmerScoreOnly ? 1 : 1000)) {
         ctx->err = "k-mer search: maxResListLen >= 1 and minDiagScoreThr >= 0 required"; return FSGPU_E_UNSUPPORTED;
     }
@@ -1115,7 +1152,7 @@ extern "C" int fsgpu_kmer_search(fsgpu_ctx *ctx, const fsgpu_kmer_search_params 
         const int left = nq - q0, parts = (left + batch - 1) / batch;
         const int m = (left + parts - 1) / parts;
         const uint64_t hitsBefore = ctx->kmerCounts[1];
-        int rc = kmerBatch(ctx, *p, queries + q0, m, out + (size_t) q0 * p->maxResListLen, nout + q0, status + q0, stats ? stats + (size_t) q0 * 4 : nullptr);
+        int rc = kmerBatch(ctx, *p, queries + q0, pq ? pq + q0 : nullptr, m, out + (size_t) q0 * p->maxResListLen, nout + q0, status + q0, stats ? stats + (size_t) q0 * 4 : nullptr);
         if (rc == kKmerHalve) { ctx->kmerBatchCap = std::max(1, m / 2); ctx->kmerBatchOk = 0; continue; }            // too many hits / out of memory: redo with half the queries
         if (rc != FSGPU_OK) return rc;
         if (ctx->kmerBatches++ == 0) ctx->kmerFirstBatchQueries = (uint32_t) m;
@@ -1129,3 +1166,89 @@ extern "C" int fsgpu_kmer_search(fsgpu_ctx *ctx, const fsgpu_kmer_search_params 
     return FSGPU_OK;
 }
 
+
+extern "C" int fsgpu_kmer_search(fsgpu_ctx *ctx, const fsgpu_kmer_search_params *p, const fsgpu_kmer_query *queries, int nq,
+                                 fsgpu_kmer_hit *out, int32_t *nout, int32_t *status, double *stats) {
+    if (!ctx || !p || (nq > 0 && (!queries || !out || !nout || !status))) return FSGPU_E_ARG;
+    if (!ctx->kidx) { ctx->err = "k-mer index not built"; return FSGPU_E_NODB; }
+    return kmerSearch(ctx, p, queries, nullptr, nq, out, nout, status, stats);
+}
+
+// ---- profile queries -------------------------------------------------------------------------------------------------------------------
+// Util::rankedDescSort20 (M/src/commons/Util.cpp:118-144): Batcher's merge-exchange network for 20 inputs, every comparator swapping only when
+// the left value is SMALLER than the right one; the letter travels with its score.  Equal scores stay where the network leaves them, and that
+// order reaches the results (it is the order of the similar k-mers), so the comparators are applied exactly in this sequence.
+static const uint8_t kSort20[][2] = {
+    {0, 16}, {1, 17}, {2, 18}, {3, 19}, {4, 12}, {5, 13}, {6, 14}, {7, 15},
+    {0, 8}, {1, 9}, {2, 10}, {3, 11},
+    {8, 16}, {9, 17}, {10, 18}, {11, 19}, {0, 4}, {1, 5}, {2, 6}, {3, 7},
+    {8, 12}, {9, 13}, {10, 14}, {11, 15}, {4, 16}, {5, 17}, {6, 18}, {7, 19}, {0, 2}, {1, 3},
+    {4, 8}, {5, 9}, {6, 10}, {7, 11}, {12, 16}, {13, 17}, {14, 18}, {15, 19}, {0, 1},
+    {4, 6}, {5, 7}, {8, 10}, {9, 11}, {12, 14}, {13, 15}, {16, 18}, {17, 19},
+    {2, 16}, {3, 17}, {6, 12}, {7, 13}, {18, 19},
+    {2, 8}, {3, 9}, {10, 16}, {11, 17},
+    {2, 4}, {3, 5}, {6, 8}, {7, 9}, {10, 12}, {11, 13}, {14, 16}, {15, 17},
+    {2, 3}, {4, 5}, {6, 7}, {8, 9}, {10, 11}, {12, 13}, {14, 15}, {16, 17},
+    {1, 16}, {3, 18}, {5, 12}, {7, 14},
+    {1, 8}, {3, 10}, {9, 16}, {11, 18},
+    {1, 4}, {3, 6}, {5, 8}, {7, 10}, {9, 12}, {11, 14}, {13, 16}, {15, 18},
+    {1, 2}, {3, 4}, {5, 6}, {7, 8}, {9, 10}, {11, 12}, {13, 14}, {15, 16}, {17, 18}};
+
+extern "C" int fsgpu_kmer_profile_sort_rows(const int8_t *scores, int L, uint16_t *rows) {
+    if (L < 0 || (L > 0 && (!scores || !rows))) return FSGPU_E_ARG;
+    for (int i = 0; i < L; i++) {
+        int v[20], a[20];
+        for (int j = 0; j < 20; j++) { v[j] = scores[(size_t) i * 20 + j]; a[j] = j; }
+        for (const uint8_t (&c)[2] : kSort20)
+            if (v[c[0]] < v[c[1]]) { std::swap(v[c[0]], v[c[1]]); std::swap(a[c[0]], a[c[1]]); }
+        for (int j = 0; j < 20; j++) rows[(size_t) i * 20 + j] = (uint16_t) ((v[j] << 8) | a[j]);
+    }
+    return FSGPU_OK;
+}
+
+extern "C" int fsgpu_kmer_search_profile(fsgpu_ctx *ctx, const fsgpu_kmer_search_params *p, const fsgpu_kmer_profile_query *queries, int nq,
+                                         fsgpu_kmer_hit *out, int32_t *nout, int32_t *status, double *stats) {
+    if (!ctx || !p || (nq > 0 && (!queries || !out || !nout || !status))) return FSGPU_E_ARG;
+    if (!ctx->kidx) { ctx->err = "k-mer index not built"; return FSGPU_E_NODB; }
+    if (ctx->kidx->p.kmerThr != 0) {
+        ctx->err = "k-mer search: a profile query needs an index built with kmerThr = 0 (Prefiltering.cpp:555: localKmerThr is 0 for profile queries, no target k-mer is dropped); "
+                   "the resident index was built with kmerThr = " + std::to_string(ctx->kidx->p.kmerThr);
+        return FSGPU_E_ARG;
+    }
+    std::vector<fsgpu_kmer_query> qs((size_t) std::max(nq, 0));
+    for (int q = 0; q < nq; q++) { qs[q] = fsgpu_kmer_query{}; qs[q].seq = queries[q].seq; qs[q].profile = queries[q].profile; qs[q].L = queries[q].L; qs[q].identity = queries[q].identity; }
+    return kmerSearch(ctx, p, qs.data(), queries, nq, out, nout, status, stats);
+}
+
+// the similar k-mers of one position of one query of the last device batch, when that was a profile batch: the list pass itself (same tables, same
+// unranking, same slices) writes the k-mers of that position instead of probing the index
+extern "C" int fsgpu_kmer_profile_list_copy(fsgpu_ctx *ctx, int query, int pos, uint32_t *kmers, uint32_t cap, uint32_t *count) {
+    if (!ctx || !count || (cap > 0 && !kmers)) return FSGPU_E_ARG;
+    if (!ctx->kidx) { ctx->err = "k-mer index not built"; return FSGPU_E_NODB; }
+    KmerScratch *S = ctx->kmer;
+    if (!S || S->profNq == 0) { ctx->err = "k-mer profile list: the last k-mer batch of this context was not a profile batch"; return FSGPU_E_ARG; }
+    if (query < 0 || query >= S->profNq || pos < 0 || (uint32_t) pos >= S->hQs.p[query].nPos) {
+        ctx->err = "k-mer profile list: query " + std::to_string(query) + " position " + std::to_string(pos) + " is not a k-mer start of the last profile batch";
+        return FSGPU_E_ARG;
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    const hipStream_t st = ctx->stream;
+    const uint32_t p = S->hQs.p[query].posBase + (uint32_t) pos;
+    uint32_t Kp = 0;
+    HIPCHK(hipMemcpyAsync(&Kp, S->K.p + p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    *count = Kp;
+    const uint32_t n = std::min(Kp, cap);
+    if (n == 0) return FSGPU_OK;
+    if (Kp > kMaxKmerResult - 1) { ctx->err = "k-mer profile list: inconsistent count"; return FSGPU_E_HIP; }
+    KDev<uint32_t> dk;
+    HIPCHK(kNew(dk, Kp));
+    const KmerIndex &ix = *ctx->kidx;
+    hipLaunchKernelGGL(k_kmer_lists_p<true>, dim3((unsigned) (S->profNPos + S->profNLists / kListSlice + 1)), dim3(kKmerBlock), 0, st, S->qs.p, S->posQuery.p, S->seqs.p, S->thrs.p,
+                       S->rows.p, S->rowBase.p, (uint32_t) S->profNPos, ix.pat, S->K.p, S->Kbase.p, ix.offsets, ix.bitmap, (uint32_t *) nullptr, (uint32_t *) nullptr,
+                       (uint32_t *) nullptr, p, dk.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(kmers, dk.p, (size_t) n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return FSGPU_OK;
+}

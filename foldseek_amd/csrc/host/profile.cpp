@@ -4,6 +4,7 @@
 #include "hostlib.h"
 
 #include <cstdio>
+#include <cstring>
 
 extern "C" {
 
@@ -35,6 +36,44 @@ int fshost_profile_decode(const char *entry, size_t len, uint8_t *codes, uint8_t
         }
     }
     return (int) L;
+}
+
+// the same, and the 20 score bytes of every position as they stand in the entry: what the k-mer generator reads (Sequence.cpp:308-310, `short` without the division)
+int fshost_profile_decode_raw(const char *entry, size_t len, uint8_t *codes, uint8_t *consensus, int8_t *profile, int8_t *profileRev, int8_t *scores, char *err, size_t errCap) {
+    const int L = fshost_profile_decode(entry, len, codes, consensus, profile, profileRev, err, errCap);
+    if (L <= 0 || !scores) return L;
+    for (int i = 0; i < L; i++) memcpy(scores + (size_t) i * 20, entry + (size_t) i * FSHOST_PROFILE_RECORD, 20);
+    return L;
+}
+
+// Prefiltering::getKmerThreshold, profile branch (Prefiltering.cpp:1050-1079; Foldseek's externalThreshold has no profile row): the products are taken
+// in double, the difference is stored in a float and cut to an int, as there
+int fshost_kmer_threshold_profile(float sensitivity, int kmerSize, int contextPseudoCounts) {
+    float base; double step;
+    if (contextPseudoCounts) {
+        if (kmerSize == 5) { base = 97.75f; step = 8.75; } else if (kmerSize == 6) { base = 132.75f; step = 8.75; } else if (kmerSize == 7) { base = 158.75f; step = 9.75; } else return -1;
+    } else {
+        if (kmerSize == 5) { base = 108.8f; step = 4.7; } else if (kmerSize == 6) { base = 134.35f; step = 6.15; } else if (kmerSize == 7) { base = 149.15f; step = 6.85; } else return -1;
+    }
+    const float best = (float) ((double) base - (double) sensitivity * step);
+    return (int) best;
+}
+
+// what fsgpu_kmer_search_profile takes of one 3Di profile entry: letters, raw score rows, the ungapped profile [L][21] (UngappedAlignment::createProfile,
+// profile branch: the alignment profile position-major, X column 0, no bias correction) and the threshold of every window, max(kmerThrBase, 0)
+int fshost_kmer_query_prepare_profile(const char *entry, size_t len, int kmerThrBase, int kmerSize, int spaced, uint8_t *codes, int8_t *scores, int8_t *profile,
+                                      int32_t *kmerThr, char *err, size_t errCap) {
+    if (kmerSize != 6) { if (err && errCap) snprintf(err, errCap, "profile k-mer query: only k = 6 is implemented (k = %d)", kmerSize); return FSHOST_PROFILE_E_ARG; }
+    const int L = fshost_profile_decode(entry, len, codes, nullptr, nullptr, nullptr, err, errCap);
+    if (L < 0) return L;
+    for (int i = 0; i < L; i++) {
+        const signed char *r = (const signed char *) entry + (size_t) i * FSHOST_PROFILE_RECORD;
+        if (scores) memcpy(scores + (size_t) i * 20, r, 20);
+        if (profile) { for (int a = 0; a < 20; a++) profile[(size_t) i * 21 + a] = (int8_t) ((int) r[a] / 4); profile[(size_t) i * 21 + 20] = 0; }
+    }
+    if (kmerThr) *kmerThr = kmerThrBase > 0 ? kmerThrBase : 0;
+    const int windows = L - (spaced ? 10 : 6) + 1;
+    return windows > 0 ? windows : 0;
 }
 
 int fshost_profile_bias(const int8_t *profile, int L) {

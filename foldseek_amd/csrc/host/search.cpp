@@ -1376,6 +1376,91 @@ int fshost_search_kmer_batch(fshost_search *s, const fshost_matrix *mKmer, const
     return FSGPU_OK;
 }
 
+// The same body for profile queries: the entries of the AA and the 3Di profile database are decoded here (fshost_profile_decode /
+// fshost_kmer_query_prepare_profile), the device prefilter is fsgpu_kmer_search_profile, what is left after the coverage pre-filter goes to
+// fshost_search_align_batch_profile.
+int fshost_search_kmer_batch_profile(fshost_search *s, const fsgpu_kmer_search_params *sp, int kmerThr, int spaced, int nq, const char *const *entryAA,
+                                     const size_t *lenAA, const char *const *entry3Di, const size_t *len3Di, const int64_t *prefIdentity,
+                                     const int64_t *alnIdentity, fsgpu_kmer_hit *hits, int32_t *nhits, int32_t *status, uint32_t *keptIds, int32_t *nkept,
+                                     fshost_result *results, int32_t *nres, double *seconds) {
+    if (!s || !s->ctx || !sp || nq < 0 || (nq > 0 && (!entryAA || !lenAA || !entry3Di || !len3Di || !hits || !nhits || !status || !keptIds || !nkept || !results || !nres))) return FSGPU_E_ARG;
+    if (sp->maxResListLen <= 0) { s->err = "fshost_search_kmer_batch_profile: maxResListLen >= 1 required"; return FSGPU_E_ARG; }
+    {   // the windows staged below are read by the device with the pattern of the RESIDENT index: another `spaced` here is refused before anything runs
+        fsgpu_kmer_index_params ip;
+        if (fsgpu_kmer_index_get_params(s->ctx, &ip) == FSGPU_OK && (spaced != 0) != (ip.spaced != 0)) {
+            s->err = "fshost_search_kmer_batch_profile: spaced = " + std::to_string(spaced) + " but the resident k-mer index was built with spaced = " + std::to_string(ip.spaced);
+            return FSGPU_E_ARG;
+        }
+    }
+    const fshost_params &par = s->par;
+    const size_t cap = (size_t) sp->maxResListLen;
+    double t0 = nowSec();
+    struct Decoded { std::vector<uint8_t> cA, c3; std::vector<int8_t> pA, pAr, p3, p3r, rows, ungapped; };
+    std::vector<Decoded> dec(nq);
+    std::vector<fsgpu_kmer_profile_query> kq(std::max(nq, 1));
+    std::vector<fshost_profile_query> pq(std::max(nq, 1));
+    std::vector<int> L(std::max(nq, 1), 0);
+    char err[256];
+    for (int k = 0; k < nq; k++) {
+        Decoded &d = dec[k];
+        const int l3 = fshost_profile_decode(entry3Di[k], len3Di[k], nullptr, nullptr, nullptr, nullptr, err, sizeof(err));
+        if (l3 < 0) { s->err = "fshost_search_kmer_batch_profile: query " + std::to_string(k) + ": " + err; return FSGPU_E_ARG; }
+        const size_t n = (size_t) l3;
+        d.cA.resize(n + 1); d.c3.resize(n + 1); d.pA.resize(21 * n + 1); d.pAr.resize(21 * n + 1); d.p3.resize(21 * n + 1); d.p3r.resize(21 * n + 1);
+        d.rows.resize(20 * n + 1); d.ungapped.resize(21 * n + 1);
+        const int lA = fshost_profile_decode(entryAA[k], lenAA[k], d.cA.data(), nullptr, d.pA.data(), d.pAr.data(), err, sizeof(err));
+        if (lA < 0) { s->err = "fshost_search_kmer_batch_profile: query " + std::to_string(k) + ": " + err; return FSGPU_E_ARG; }
+        if (lA != l3) { s->err = "fshost_search_kmer_batch_profile: query " + std::to_string(k) + ": the AA and the 3Di profile differ in length"; return FSGPU_E_ARG; }
+        fshost_profile_decode(entry3Di[k], len3Di[k], nullptr, nullptr, d.p3.data(), d.p3r.data(), nullptr, 0);
+        int32_t thr = 0;
+        fshost_kmer_query_prepare_profile(entry3Di[k], len3Di[k], kmerThr, 6, spaced, d.c3.data(), d.rows.data(), d.ungapped.data(), &thr, nullptr, 0);
+        L[k] = l3;
+        kq[k] = fsgpu_kmer_profile_query{d.c3.data(), d.rows.data(), d.ungapped.data(), l3, thr, prefIdentity ? prefIdentity[k] : -1};
+        pq[k] = fshost_profile_query{d.cA.data(), d.c3.data(), d.pA.data(), d.pAr.data(), d.p3.data(), d.p3r.data(), l3, 0};
+    }
+    double t1 = nowSec();
+    if (seconds) seconds[0] = t1 - t0;
+    t0 = t1;
+    if (nq > 0) {
+        const int rc = fsgpu_kmer_search_profile(s->ctx, sp, kq.data(), nq, hits, nhits, status, nullptr);
+        if (rc != FSGPU_OK) { s->err = fsgpu_last_error(s->ctx); return rc; }
+    }
+    t1 = nowSec();
+    if (seconds) seconds[1] = t1 - t0;
+    t0 = t1;
+    const bool cov = par.covThr > 0.0 && (par.covMode == 0 || par.covMode == 2 || par.covMode == 5);
+    std::vector<fshost_profile_query> lP;
+    std::vector<const uint32_t *> lT;
+    std::vector<fshost_result *> lR;
+    std::vector<int> lN, lres, lq;
+    std::vector<int64_t> lI;
+    for (int k = 0; k < nq; k++) {
+        nres[k] = 0; nkept[k] = 0;
+        if (status[k] < 0) continue;
+        uint32_t *ids = keptIds + (size_t) k * cap;
+        int n = 0;
+        for (int h = 0; h < nhits[k]; h++) {
+            const fsgpu_kmer_hit &hit = hits[(size_t) k * cap + h];
+            if (cov && !kmerCanBeCovered((float) par.covThr, par.covMode, (float) L[k], (float) s->lengths[hit.id])) continue;
+            ids[n++] = hit.id;
+        }
+        nkept[k] = n;
+        if (n == 0 || L[k] <= 0) continue;
+        lq.push_back(k); lP.push_back(pq[k]); lT.push_back(ids); lR.push_back(results + (size_t) k * cap); lN.push_back(n); lI.push_back(alnIdentity ? alnIdentity[k] : -1);
+    }
+    t1 = nowSec();
+    if (seconds) seconds[2] = t1 - t0;
+    t0 = t1;
+    if (!lq.empty()) {
+        lres.assign(lq.size(), 0);
+        const int rc = fshost_search_align_batch_profile(s, (int) lq.size(), lP.data(), lI.data(), lT.data(), lN.data(), lR.data(), lres.data());
+        if (rc != FSGPU_OK) return rc;
+        for (size_t j = 0; j < lq.size(); j++) nres[lq[j]] = lres[j];
+    }
+    if (seconds) seconds[3] = nowSec() - t0;
+    return FSGPU_OK;
+}
+
 int fshost_search_rescore_diagonal_batch(fshost_search *s, int nq, const uint8_t *const *qAA, const uint8_t *const *q3di, const int *L,
                                          const int64_t *identityId, const uint32_t *const *targetIds, const int16_t *const *diagonals,
                                          const int *n, fshost_result *const *results, int *nres) {

@@ -530,6 +530,39 @@ enum {
 int fsgpu_kmer_search(fsgpu_ctx *ctx, const fsgpu_kmer_search_params *p, const fsgpu_kmer_query *queries, int nq,
                       fsgpu_kmer_hit *out, int32_t *nout, int32_t *status, double *stats);
 
+/* ---- profile queries in the k-mer prefilter (`prefilter <profileDB_ss> ...` with --prefilter-mode 0: every round of an iterative search after the
+ * first).  One query: the query letters seq[L] (Sequence::numSequence of the 3Di profile; a window with a letter >= 20 at one of its six pattern
+ * offsets is skipped, QueryMatcher.cpp:264), the RAW score bytes scores[L][20] of the entry (Sequence::mapProfile reads them as short without the
+ * division by four; fshost_profile_decode_raw), the ungapped profile[L][21] = score / 4 with a zero X column (UngappedAlignment::createProfile,
+ * profile branch: no bias correction), kmerThr (fshost_kmer_threshold_profile or --k-score's profile half; every position's threshold is
+ * max(kmerThr, 0): a profile has no composition bias, QueryMatcher.cpp:109-117,271) and identity as in fsgpu_kmer_query.
+ * The similar k-mers of a position are KmerGenerator::generateKmerList over the six rows of its window, each sorted by Util::rankedDescSort20 (the
+ * call sorts them while it stages the batch): all 6-tuples of row ranks whose scores sum to >= the threshold, in lexicographic order of the ranks,
+ * the first 8 388 607 of them (MAX_KMER_RESULT_SIZE - 1).  The reference computes its cutoffs in 16 bits; they wrap for a kmerThr above 31 999,
+ * which this call does not reproduce: there it gives what the rule gives without the wrap (no k-mer, as for every kmerThr above 762). */
+typedef struct {
+    const uint8_t *seq;
+    const int8_t *scores;
+    const int8_t *profile;
+    int32_t L;
+    int32_t kmerThr;
+    int64_t identity;
+} fsgpu_kmer_profile_query;
+/* fsgpu_kmer_search for profile queries: same parameters, outputs, status codes, statistics, batching and halving rule; everything behind the
+ * similar-k-mer lists is the same code.  fsgpu_kmer_last_counts / _batch_hint / _last_segments / fsgpu_last_kernel_ms read it like a sequence call.
+ * The resident index must have been built with kmerThr = 0 (Prefiltering.cpp:555-557: localKmerThr is 0 with a profile query, no target k-mer is
+ * dropped for its self-score); any other index is refused with FSGPU_E_ARG before anything is staged. */
+int fsgpu_kmer_search_profile(fsgpu_ctx *ctx, const fsgpu_kmer_search_params *p, const fsgpu_kmer_profile_query *queries, int nq,
+                              fsgpu_kmer_hit *out, int32_t *nout, int32_t *status, double *stats);
+/* Test / inspection: the similar k-mers of k-mer start `pos` of query `query` of the LAST DEVICE BATCH of this context, which must have been a profile
+ * batch (a call of more queries than one batch takes leaves its last batch; a sequence call in between leaves none: FSGPU_E_ARG).  *count receives K_p
+ * (capped); kmers[0 .. min(cap, K_p)) the k-mers in emission order, in the reference's numbering sum of letter_i * 20^i (i in pattern order).  The list
+ * pass itself writes them, with the index probes switched off. */
+int fsgpu_kmer_profile_list_copy(fsgpu_ctx *ctx, int query, int pos, uint32_t *kmers, uint32_t cap, uint32_t *count);
+/* Host only: the rows of L positions as the device reads them, rows[i * 20 + rank] = score << 8 | letter, sorted by the comparator sequence of
+ * Util::rankedDescSort20 (equal scores stay where that network leaves them: neither stable nor by letter, and visible in the results). */
+int fsgpu_kmer_profile_sort_rows(const int8_t *scores, int L, uint16_t *rows);
+
 /* Work counters of the last fsgpu_kmer_search batch: [0] similar k-mers probed in the index table, [1] index hits,
  * [2] double-diagonal candidates, [3] elements handed to the host tail. */
 void fsgpu_kmer_last_counts(const fsgpu_ctx *ctx, uint64_t *out4);

@@ -202,6 +202,16 @@ int fshost_search_kmer_batch(fshost_search *s, const fshost_matrix *mKmer, const
                              int kmerThr, int spaced, int nq, const uint8_t *const *qAA, const uint8_t *const *q3di, const int *L,
                              const int64_t *prefIdentity, const int64_t *alnIdentity, fsgpu_kmer_hit *hits, int32_t *nhits, int32_t *status,
                              uint32_t *keptIds, int32_t *nkept, fshost_result *results, int32_t *nres, double *seconds);
+/* The same body for PROFILE queries (the later rounds of an iterative search with the k-mer prefilter, structureiterativesearch.sh:24-37), in ONE call:
+ * entryAA[q] / entry3Di[q] are the query's entries of the AA and the 3Di profile database (lenAA / len3Di without the terminator); they are decoded
+ * (fshost_profile_decode, fshost_kmer_query_prepare_profile), the device prefilter is fsgpu_kmer_search_profile over the 3Di entry, runSplit's coverage
+ * pre-filter uses the profile's length, and what is left goes to fshost_search_align_batch_profile.  kmerThr: fshost_kmer_threshold_profile or --k-score's
+ * profile half.  Outputs and `spaced` as for fshost_search_kmer_batch with results [nq * cap] (alternative alignments are refused for profile queries).
+ * The resident k-mer index must have been built with kmerThr = 0 (fsgpu_kmer_search_profile refuses another one). */
+int fshost_search_kmer_batch_profile(fshost_search *s, const fsgpu_kmer_search_params *sp, int kmerThr, int spaced, int nq, const char *const *entryAA,
+                                     const size_t *lenAA, const char *const *entry3Di, const size_t *len3Di, const int64_t *prefIdentity,
+                                     const int64_t *alnIdentity, fsgpu_kmer_hit *hits, int32_t *nhits, int32_t *status, uint32_t *keptIds, int32_t *nkept,
+                                     fshost_result *results, int32_t *nres, double *seconds);
 /* structurerescorediagonal for nq queries (F/src/strucclustutils/structurerescorediagonal.cpp:50-156,300-370): targetIds / diagonals
  * are the first and third column of the prefilter lines in their order; results[q] has room for n[q] entries; gates, e-value,
  * seq. id, ordering and (with addBacktrace) the all-match backtrace as the module writes them.  identityId[q]: the target INDEX that is query q
@@ -275,6 +285,19 @@ int fshost_banded_backtrace(const fshost_matrix *mAA, const fshost_matrix *m3Di,
 #define FSHOST_PROFILE_E_LENGTH (-2)
 #define FSHOST_PROFILE_E_LETTER (-3)
 int fshost_profile_decode(const char *entry, size_t len, uint8_t *codes, uint8_t *consensus, int8_t *profile, int8_t *profileRev, char *err, size_t errCap);
+/* fshost_profile_decode, and scores[L][20]: the 20 score bytes of every position as they stand in the entry, position-major -- what the k-mer generator
+ * reads (Sequence.cpp:308-310: as short, NOT divided by four).  scores may be NULL. */
+int fshost_profile_decode_raw(const char *entry, size_t len, uint8_t *codes, uint8_t *consensus, int8_t *profile, int8_t *profileRev, int8_t *scores,
+                              char *err, size_t errCap);
+/* Prefiltering::getKmerThreshold for a profile query (Prefiltering.cpp:1050-1079): int(132.75 - 8.75 s) at k = 6 with context pseudo-counts,
+ * int(134.35 - 6.15 s) without; k = 5 and 7 as there, -1 for another k.  --k-score's profile half, when set, replaces it (the caller's choice). */
+int fshost_kmer_threshold_profile(float sensitivity, int kmerSize, int contextPseudoCounts);
+/* One 3Di profile entry as fsgpu_kmer_search_profile takes it: codes[L] the query letters, scores[L][20] the raw score rows, profile[L][21] the ungapped
+ * profile (UngappedAlignment::createProfile, profile branch: score / 4 position-major, X column 0, no bias correction), *kmerThr = max(kmerThrBase, 0),
+ * the threshold of every window (a profile has no composition bias).  Any output may be NULL.  Returns the number of windows max(0, L - pattern + 1)
+ * (pattern = 10 with spaced, 6 without), or a FSHOST_PROFILE_E_* code with the reason in err; only kmerSize = 6 is implemented. */
+int fshost_kmer_query_prepare_profile(const char *entry, size_t len, int kmerThrBase, int kmerSize, int spaced, uint8_t *codes, int8_t *scores, int8_t *profile,
+                                      int32_t *kmerThr, char *err, size_t errCap);
 /* The bias of the profile branch of SmithWaterman::ssw_init (StripedSmithWaterman.cpp:1397-1406): minus the smallest of the 20 x L scores, 0 when none
  * is negative; there is no composition bias.  The gapless scan of a profile query (ungappedprefilter.cpp:381-384) runs with this pssm and the score
  * cap 255 - bias. */
