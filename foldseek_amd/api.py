@@ -79,6 +79,11 @@ class BtRes(C.Structure):
                 ("blockSizes", C.c_int32), ("btOff", C.c_uint64)]
 
 
+class PbtQuery(C.Structure):
+    """fsgpu_pbt_query"""
+    _fields_ = [("pAA", C.c_void_p), ("p3Di", C.c_void_p), ("lettersAA", C.c_void_p), ("L", C.c_int32), ("reserved", C.c_int32)]
+
+
 class LddtQuery(C.Structure):
     """fsgpu_lddt_query"""
     _fields_ = [("ca", C.c_void_p), ("L", C.c_int32), ("reserved", C.c_int32)]
@@ -135,6 +140,8 @@ def lib():
         "fsgpu_live_devices": (i32, []),
         "fsgpu_block_backtrace": (i32, [vp, vp, vp, vp, vp, C.POINTER(BtQuery), i32, C.POINTER(BtTask), i32, i32, i32, C.POINTER(BtRes), C.POINTER(C.c_void_p)]),
         "fsgpu_block_backtrace_footprint": (i32, [vp, i32]),
+        "fsgpu_profile_backtrace": (i32, [vp, C.POINTER(PbtQuery), i32, C.POINTER(BtTask), i32, i32, i32, C.POINTER(BtRes), C.POINTER(C.c_void_p)]),
+        "fsgpu_profile_backtrace_last": (None, [vp, vp]),
         "fsgpu_lddt_batch": (i32, [vp, C.POINTER(LddtQuery), i32, C.POINTER(LddtTask), i32, vp, u64, vp, u64, vp, vp, u64]),
         "fsgpu_tm_batch": (i32, [vp, C.POINTER(LddtQuery), i32, C.POINTER(TmTask), i32, vp, u64, vp, u64, vp, vp, vp]),
         "fsgpu_tm_superpose_batch": (i32, [vp, C.POINTER(LddtQuery), i32, C.POINTER(TmTask), i32, vp, u64, vp, u64, i32, C.POINTER(TmResult)]),
@@ -268,7 +275,7 @@ def exported_symbols():
     return ["fsgpu_create", "fsgpu_destroy", "fsgpu_last_error", "fsgpu_device", "fsgpu_stream", "fsgpu_db_load",
             "fsgpu_db_adopt_device", "fsgpu_db_check_table", "fsgpu_db_size", "fsgpu_db_residues", "fsgpu_gapless_scan", "fsgpu_gapless_scores",
             "fsgpu_gapless_launch", "fsgpu_gapless_finish", "fsgpu_sw_batch", "fsgpu_sw_multi", "fsgpu_sw_multi_dir", "fsgpu_sw_multi_dir_c", "fsgpu_sw_multi_c", "fsgpu_sw_multi_dir_p", "fsgpu_sw_multi_p", "fsgpu_sw_launch", "fsgpu_sw_finish",
-            "fsgpu_db_broadcast", "fsgpu_rccl_selfcheck", "fsgpu_device_count", "fsgpu_live_devices", "fsgpu_gapless_plan_items", "fsgpu_gapless_item_records", "fsgpu_gapless_pair_halves", "fsgpu_gapless_shape", "fsgpu_block_backtrace", "fsgpu_block_backtrace_footprint",
+            "fsgpu_db_broadcast", "fsgpu_rccl_selfcheck", "fsgpu_device_count", "fsgpu_live_devices", "fsgpu_gapless_plan_items", "fsgpu_gapless_item_records", "fsgpu_gapless_pair_halves", "fsgpu_gapless_shape", "fsgpu_block_backtrace", "fsgpu_block_backtrace_footprint", "fsgpu_profile_backtrace", "fsgpu_profile_backtrace_last",
             "fsgpu_lddt_batch", "fsgpu_tm_batch", "fsgpu_tm_superpose_batch", "fsgpu_last_kernel_ms", "fsgpu_history_counters", "fsgpu_sw_last_passes", "fsgpu_sw3_last_plan", "fsgpu_kmer_index_build", "fsgpu_kmer_index_entries", "fsgpu_kmer_index_entry_bytes", "fsgpu_kmer_index_get_params", "fsgpu_kmer_search",
             "fsgpu_kmer_index_copy", "fsgpu_kmer_row_copy", "fsgpu_kmer_last_counts", "fsgpu_kmer_last_segments", "fsgpu_kmer_plan_coarse", "fsgpu_kmer_batch_hint",
             "fsgpu_kmer_search_profile", "fsgpu_kmer_profile_list_copy", "fsgpu_kmer_profile_sort_rows",
@@ -954,6 +961,47 @@ class Context:
             bt = C.string_at(base.value + r.btOff, r.btLen).decode() if r.status == 1 and r.btLen > 0 else ""
             out.append(dict(status=r.status, qStart=r.qStart, dbStart=r.dbStart, identicalAA=r.identicalAA, blockSizes=r.blockSizes, backtrace=bt))
         return out
+
+    def profile_backtrace(self, queries, tasks, gap_open=10, gap_extend=1):
+        """fsgpu_profile_backtrace called directly: start cell, identity count and M / I / D string of accepted hits of profile queries.  queries: list of
+        (pAA int8 [21, L], p3Di int8 [21, L], lettersAA uint8 [L]) -- the forward alignment profiles; tasks: list of (query, target, qEnd, dbEnd, score)
+        with targets of the resident DB.  Returns one dict per task: status (1 answered, 2 reverse pass differs, 3 no path, 0 handed back), qStart,
+        dbStart, identicalAA, band (the width the banded pass ended with) and the backtrace, copied out before the next call can overwrite it.  A refusal
+        raises FsgpuError with .rc and .res: the result records as the call left them (filled with -7 before it)."""
+        nq, nt = len(queries), len(tasks)
+        qs, keep = (PbtQuery * max(nq, 1))(), []
+        for i, (pa, p3, let) in enumerate(queries):
+            bufs = (np.ascontiguousarray(pa, np.int8), np.ascontiguousarray(p3, np.int8), np.ascontiguousarray(let, np.uint8))
+            L = len(bufs[2])
+            if bufs[0].size != 21 * L or bufs[1].size != 21 * L:
+                raise FsgpuError(f"profile_backtrace: query {i}: tables must be int8 [21, L] for L letters")
+            keep.append(bufs)
+            qs[i].pAA, qs[i].p3Di, qs[i].lettersAA = [b.ctypes.data for b in bufs]
+            qs[i].L, qs[i].reserved = L, 0
+        ts = (BtTask * max(nt, 1))()
+        for k, (q, t, qe, de, sc) in enumerate(tasks):
+            ts[k].query, ts[k].target, ts[k].qEnd, ts[k].dbEnd, ts[k].score = int(q) & 0xFFFFFFFF, int(t) & 0xFFFFFFFF, int(qe), int(de), int(sc)
+        res = (BtRes * max(nt, 1))()
+        C.memset(res, 0xF9, C.sizeof(res))
+        base = C.c_void_p()
+        rc = lib().fsgpu_profile_backtrace(self.h, qs, nq, ts, nt, int(gap_open), int(gap_extend), res, C.byref(base))
+        if rc != 0:
+            e = FsgpuError(f"fsgpu_profile_backtrace rc={rc}: {lib().fsgpu_last_error(self.h).decode()}")
+            e.rc, e.res = rc, bytes(res)
+            raise e
+        out = []
+        for k in range(nt):
+            r = res[k]
+            bt = C.string_at(base.value + r.btOff, r.btLen).decode() if r.status == 1 and r.btLen > 0 else ""
+            out.append(dict(status=r.status, qStart=r.qStart, dbStart=r.dbStart, identicalAA=r.identicalAA, band=r.blockSizes, backtrace=bt))
+        return out
+
+    def profile_backtrace_last(self):
+        """fsgpu_profile_backtrace_last: what the last profile_backtrace call of this context did"""
+        o = np.zeros(8)
+        lib().fsgpu_profile_backtrace_last(self.h, _ptr(o))
+        return {"launches": int(o[0]), "status": [int(o[1]), int(o[2]), int(o[3]), int(o[4])], "device_ms": float(o[5]), "scratch_bytes": int(o[6]),
+                "band_launches": int(o[7])}
 
     def lddt_batch(self, queries, targets, tasks):
         """fsgpu_lddt_batch called directly: the reference's per-residue LDDT values of a batch of hits.  queries / targets: lists of float32

@@ -84,7 +84,7 @@ void fsgpu_destroy(fsgpu_ctx *ctx) {
     DevBuf *bufs[] = {&ctx->gBorder0, &ctx->gBorder1, &ctx->scoreAcc, &ctx->pssm, &ctx->scores, &ctx->chunkHist, &ctx->baseGt, &ctx->baseTie, &ctx->outId, &ctx->outScore,
                       &ctx->img, &ctx->tids, &ctx->res0, &ctx->res1, &ctx->border0, &ctx->border1, &ctx->keys, &ctx->lbuf, &ctx->lres,
                       &ctx->ovAA, &ctx->ovSS, &ctx->ovOff, &ctx->ovLen, &ctx->s3img, &ctx->s3pass, &ctx->s3build, &ctx->s3res,
-                      &ctx->btSeq, &ctx->btTrace, &ctx->btBlocks, &ctx->btOut, &ctx->btIn, &ctx->ldIn, &ctx->ldNorm, &ctx->ldCols, &ctx->ldOut,
+                      &ctx->btSeq, &ctx->btTrace, &ctx->btBlocks, &ctx->btOut, &ctx->btIn, &ctx->pbtIn, &ctx->pbtTasks, &ctx->pbtState, &ctx->pbtDir, &ctx->pbtOut, &ctx->ldIn, &ctx->ldNorm, &ctx->ldCols, &ctx->ldOut,
                       &ctx->tmIn, &ctx->tmPairs, &ctx->tmMasks, &ctx->tmOut, &ctx->tmParts,
                       &ctx->mqPssm, &ctx->mqScores, &ctx->mqQueues, &ctx->mqRec, &ctx->mqHist, &ctx->mqBaseGt, &ctx->mqBaseTie, &ctx->mqMeta,
                       &ctx->mqOutId, &ctx->mqOutScore, &ctx->mqIdent, &ctx->scanCnt, &ctx->scanMeta, &ctx->scanOut};
@@ -95,6 +95,8 @@ void fsgpu_destroy(fsgpu_ctx *ctx) {
     hipHostFree(ctx->hS3pass.p); hipHostFree(ctx->hS3build.p); hipHostFree(ctx->hS3res.p);
     hipHostFree(ctx->hBtIn.p); hipHostFree(ctx->hBtOut.p); hipHostFree(ctx->hLdIn.p); hipHostFree(ctx->hLdOut.p);
     hipHostFree(ctx->hTmIn.p); hipHostFree(ctx->hTmOut.p);
+    hipHostFree(ctx->hPbtIn.p); hipHostFree(ctx->hPbtTasks.p); hipHostFree(ctx->hPbtOut.p);
+    for (int i = 0; i < 2; i++) if (ctx->pbtEv[i]) (void) hipEventDestroy(ctx->pbtEv[i]);
     hipHostFree(ctx->hScanMeta.p); hipHostFree(ctx->hScanOut.p);
     for (int i = 0; i < 4; i++) if (ctx->scanEv[i]) (void) hipEventDestroy(ctx->scanEv[i]);
     for (int i = 0; i < 3; i++) if (ctx->tmEv[i]) (void) hipEventDestroy(ctx->tmEv[i]);

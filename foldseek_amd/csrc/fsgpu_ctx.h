@@ -158,6 +158,12 @@ struct fsgpu_ctx {
     int btWgPerCU = 0;                          // fsgpu_block_backtrace_footprint: workgroups per CU of k_block_backtrace (0: default)
     DevBuf btSeq, btTrace, btBlocks, btOut, btIn;  // fsgpu_block_backtrace (k_btrace.hpp): padded reversed prefixes, trace words, block lists, [backtraces | results], inputs
     PinBuf hBtIn, hBtOut;
+    // fsgpu_profile_backtrace (k_pbtrace.hpp): [query tables and letters | descriptors], the tasks of a launch, global line state, direction bytes,
+    // [backtraces | results]; events around a launch; what the last call did (fsgpu_profile_backtrace_last)
+    DevBuf pbtIn, pbtTasks, pbtState, pbtDir, pbtOut;
+    PinBuf hPbtIn, hPbtTasks, hPbtOut;
+    hipEvent_t pbtEv[2] = {nullptr, nullptr};
+    double pbtLast[8] = {};
     // fsgpu_lddt_batch (k_lddt.hpp): [query coordinates | target coordinates | backtraces | descriptors], per-residue norms, per-column workspace,
     // [per-column scores | alignment lengths]; host-side planning arrays kept between calls; device ms of the last call's two kernels
     DevBuf ldIn, ldNorm, ldCols, ldOut;

@@ -804,6 +804,7 @@ struct PreBacktrace {
     std::vector<std::vector<int>> idx;       // [query][pair] -> outs index or -1
     double seconds = 0;                       // wall time of the parallel section
     size_t onDevice = 0;                      // hits the device aligner answered
+    size_t allTasks = 0;                      // profile batches: hits handed to the device entry (those it handed back included)
 };
 void precomputeBacktraces(const fshost_search *s, const std::vector<AlignQuery> &aq, const uint32_t *const *targetIds, const int *n,
                           const fsgpu_swres *fwd, const fsgpu_swres *rev, PreBacktrace &pb) {
@@ -971,6 +972,68 @@ void precomputeBacktraces(const fshost_search *s, const std::vector<AlignQuery> 
     }
     pb.onDevice = devDone.load();
     pb.seconds = nowSec() - t0;
+}
+
+// The same for profile queries: start cell, identity count and path of every pair that passes the score gates from ONE fsgpu_profile_backtrace call
+// (k_pbtrace.hpp) instead of a device round trip and a scalar banded DP per hit inside gateAlign.  The no-cigar rule stays here: below the coverage
+// threshold from start to end (:684-688) the path is dropped and the start cell kept.  A task the device hands back (status 0: beyond the scratch
+// budget) keeps idx = -1 and gateAlign answers it through profileBacktrace; a reverse pass that does not reproduce the score is the error it is there.
+// FSGPU_PROFILE_BACKTRACE = 0 keeps the one-by-one path for every hit (read per call: the tests switch it inside one process).
+int precomputeProfileBacktraces(fshost_search *s, const std::vector<AlignQuery> &aq, const uint32_t *const *targetIds, const int *n,
+                                const fsgpu_swres *fwd, const fsgpu_swres *rev, PreBacktrace &pb) {
+    const int nq = (int) aq.size();
+    pb.idx.assign(nq, {});
+    if (s->par.maxAccept != INT_MAX || s->par.maxRejected != INT_MAX) return FSGPU_OK;
+    const char *env = getenv("FSGPU_PROFILE_BACKTRACE");
+    if (env && *env && atoi(env) == 0) return FSGPU_OK;
+    if (!s->dataAA) return FSGPU_OK;                        // a database without AA sequences: the host path reads X there
+    const fshost_params &par = s->par;
+    struct Task { int q, k; };
+    std::vector<Task> where;
+    std::vector<fsgpu_bt_task> bt;
+    size_t base = 0;
+    for (int i = 0; i < nq; i++) {
+        pb.idx[i].assign(n[i], -1);
+        for (int k = 0; k < n[i]; k++) {
+            const uint32_t tid = targetIds[i][k];
+            const fsgpu_swres &f = fwd[base + k];
+            if (tid >= s->keys.size()) continue;
+            int32_t score; double evalue;
+            if (!passesScoreGates(s, aq[i], tid, f, rev[base + k], score, evalue, nullptr)) continue;
+            if (f.qEnd < 0 || f.qEnd >= aq[i].L || f.dbEnd < 0 || f.dbEnd >= s->lengths[tid]) continue;      // profileBacktrace names the error
+            where.push_back({i, k});
+            bt.push_back(fsgpu_bt_task{(uint32_t) i, tid, f.qEnd, f.dbEnd, f.score});
+        }
+        base += (size_t) n[i];
+    }
+    pb.outs.clear();
+    if (bt.empty()) return FSGPU_OK;
+    const double t0 = nowSec();
+    std::vector<fsgpu_pbt_query> pq(nq);
+    for (int i = 0; i < nq; i++) { pq[i].pAA = aq[i].prof->pAA; pq[i].p3Di = aq[i].prof->p3Di; pq[i].lettersAA = aq[i].prof->codesAA; pq[i].L = aq[i].L; pq[i].reserved = 0; }
+    std::vector<fsgpu_bt_res> br(bt.size());
+    const char *btBase = nullptr;
+    const int rc = fsgpu_profile_backtrace(s->ctx, pq.data(), nq, bt.data(), (int) bt.size(), par.gapOpen, par.gapExtend, br.data(), &btBase);
+    if (rc != FSGPU_OK) { s->err = fsgpu_last_error(s->ctx); return rc; }
+    pb.outs.reserve(bt.size());
+    for (size_t t = 0; t < bt.size(); t++) {
+        const fsgpu_bt_res &r = br[t];
+        if (r.status == 0) continue;
+        if (r.status == 2) { s->err = "profile backtrace: score of forward / backward SW differ"; return FSGPU_E_ARG; }
+        const AlignQuery &a = aq[where[t].q];
+        BlockAlnOut o;
+        o.ok = true; o.qStart = r.qStart; o.dbStart = r.dbStart;
+        if (r.status == 1 && hasCoverage(par.covThr, par.covMode, computeCov(r.qStart, bt[t].qEnd, a.L), computeCov(r.dbStart, bt[t].dbEnd, s->lengths[bt[t].target]))) {
+            o.identicalAA = (unsigned int) r.identicalAA;
+            o.backtrace.assign(btBase + r.btOff, (size_t) r.btLen);
+        }
+        pb.idx[where[t].q][where[t].k] = (int) pb.outs.size();
+        pb.outs.push_back(std::move(o));
+        pb.onDevice++;
+    }
+    pb.allTasks = bt.size();
+    pb.seconds = nowSec() - t0;
+    return FSGPU_OK;
 }
 
 // LDDT of the precomputed backtraces of the batch in one device call, for exactly the hits gateAlign will ask about: those that pass checkCriteria
@@ -1151,8 +1214,9 @@ int fshost_search_align_batch(fshost_search *s, int nq, const uint8_t *const *qA
 }
 
 // The same for profile queries (fshost.h): no composition bias, mu / lambda from the 3Di profile's query letters, scores from the tables through
-// fsgpu_sw_multi_p / _dir_p, the same needsReversePass and gateAlign; the backtraces come from profileBacktrace inside gateAlign, one by one: each
-// starts with a device call on the handle's context, so the host pool's precomputation (precomputeBacktraces) is not used.
+// fsgpu_sw_multi_p / _dir_p, the same needsReversePass and gateAlign; the backtraces of all hits that pass the score gates come from one
+// fsgpu_profile_backtrace call (precomputeProfileBacktraces).  With --max-accept / --max-rejected, with FSGPU_PROFILE_BACKTRACE=0 and for a hit the device
+// hands back they come from profileBacktrace inside gateAlign, one by one: each starts with a device call on the handle's context.
 int fshost_search_align_batch_profile(fshost_search *s, int nq, const fshost_profile_query *q, const int64_t *identityId,
                                       const uint32_t *const *targetIds, const int *n, fshost_result *const *results, int *nres) {
     if (!s || !s->ctx || nq < 0 || (nq > 0 && (!q || !targetIds || !n || !results || !nres))) return FSGPU_E_ARG;
@@ -1208,14 +1272,18 @@ int fshost_search_align_batch_profile(fshost_search *s, int nq, const fshost_pro
     const double t2 = nowSec();
     double tBack = 0;
     s->cigars.clear();
+    PreBacktrace pb;
+    if ((rc = precomputeProfileBacktraces(s, aq, targetIds, n, s->fwd.data(), s->rev.data(), pb)) != FSGPU_OK) return rc;
+    tBack += pb.seconds;
     size_t base = 0;
     for (int i = 0; i < nq; i++) {
-        nres[i] = gateAlign(s, aq[i], identityId ? identityId[i] : -1, targetIds[i], n[i], s->fwd.data() + base, s->rev.data() + base, results[i], tBack, nullptr, nullptr);
+        nres[i] = gateAlign(s, aq[i], identityId ? identityId[i] : -1, targetIds[i], n[i], s->fwd.data() + base, s->rev.data() + base, results[i], tBack,
+                            pb.outs.data(), pb.idx[i].empty() ? nullptr : pb.idx[i].data());
         if (nres[i] < 0) return nres[i];
         base += (size_t) n[i];
     }
     s->stats[2] = t1 - t0; s->stats[3] = t2 - t1; s->stats[5] = tBack; s->stats[4] = nowSec() - t2 - tBack;
-    s->lastDeviceBt = 0; s->lastBtTasks = 0;
+    s->lastDeviceBt = (int64_t) pb.onDevice; s->lastBtTasks = (int64_t) pb.allTasks;
     return FSGPU_OK;
 }
 

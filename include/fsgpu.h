@@ -362,6 +362,31 @@ int fsgpu_block_backtrace(fsgpu_ctx *ctx, const int8_t *tblAA, const int8_t *tbl
  * and three waves per SIMD for the 10-20 ms of a call).  1 leaves two thirds of a CU's LDS and most issue slots to the kernels of other contexts: what a
  * caller that shares a batch between its host threads and the device asks for (fshost_search_align_batch with FSGPU_DEVICE_BACKTRACE=2). */
 int fsgpu_block_backtrace_footprint(fsgpu_ctx *ctx, int workgroupsPerCU);
+/* ---- start cell + banded trace-back of accepted hits of PROFILE queries ------------------------------------------------------------
+ * StructureSmithWaterman::alignStartPosBacktrace<PROFILE> (F/src/commons/StructureSmithWaterman.cpp:540-739; banded_sw :1723-1957, computerBacktrace
+ * :746-773) for a batch of hits, which structurealign takes instead of the block aligner when the query database holds profiles.  Per task: the
+ * affine SW recurrence over the reversed profile prefix [0, qEnd] x the reversed target prefix [0, dbEnd] in int32, stopped at the first column whose
+ * maximum reaches `score` (its smallest row: the start cell); then the banded pass over [qStart, qEnd] x [dbStart, dbEnd], band |dbLen - qLen| + 1
+ * doubled until the best score reaches `score`, its trace-back from the end cell, and the identities against lettersAA.  pAA / p3Di: the FORWARD alignment
+ * profiles [21 * L] (X row included), read in place by both passes; target letters come from the resident database.  Tasks and results are those of
+ * fsgpu_block_backtrace; blockSizes carries the band width the banded pass ended with.
+ * status 1: qStart / dbStart / identicalAA and btLen characters at *btBase + btOff (valid until the next call on this context);
+ * status 2: the reverse pass did not reproduce `score` (the reference exits there): no start cell;
+ * status 3: start cell set, no path: the trace-back met a cell outside the band or an impossible direction, or the whole rectangle does not reach `score`;
+ * status 0: not computed here, the caller runs its host path -- the task does not fit the scratch budget at the band it needs (blockSizes: that band).
+ * Scratch: one direction byte per band cell, qLen x min(2 band + 1, dbLen) per task (slices are sized for two doublings ahead where the budget has room;
+ * a band that outgrows its slice re-runs in a later launch of the same call), plus 8 bytes per line cell for lines beyond 1024 cells.  The budget of one
+ * launch is FSGPU_PBT_BYTES (read per call; default 268435456 = 256 MiB: a module batch of 64 queries x 50 hits of 300 x 300 cells at 4 x its
+ * first band stays below it, and eight feeder contexts of a device together stay below 2 GiB); a call whose tasks exceed it runs in several launches.
+ * Refused with nothing launched and res untouched, FSGPU_E_ARG: a query index, target id or end cell out of range, gapOpen <= gapExtend or
+ * gapExtend < 1; FSGPU_E_NODB: no database, or one loaded without AA sequences; FSGPU_E_UNSUPPORTED: gapOpen >= 32768 (the limit of the SW entries whose
+ * records the tasks come from; the kernels' "no value" of -2^29 and their gap-cost products are sized for it).  nt == 0 is FSGPU_OK. */
+typedef struct { const int8_t *pAA, *p3Di; const uint8_t *lettersAA; int32_t L; int32_t reserved; } fsgpu_pbt_query;
+int fsgpu_profile_backtrace(fsgpu_ctx *ctx, const fsgpu_pbt_query *queries, int nq, const fsgpu_bt_task *tasks, int nt,
+                            int gapOpen, int gapExtend, fsgpu_bt_res *res, const char **btBase);
+/* The last fsgpu_profile_backtrace call of the context: [0] kernel launches, [1..4] tasks that came back with status 0, 1, 2, 3, [5] device milliseconds of
+ * the launches (events), [6] scratch bytes of its largest launch, [7] launches of the banded pass among [0]. */
+void fsgpu_profile_backtrace_last(const fsgpu_ctx *ctx, double *out8);
 /* Number of devices that hold at least one live context of this process (a module run with --gpus 8 : 8).  The host side divides the cores the process may
  * use by it when it decides who computes the backtraces (FSGPU_CORES_PER_GPU overrides the quotient: one rank of a multi-process job sets it to its share). */
 int fsgpu_live_devices(void);
